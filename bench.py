@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the SlicedNonbondedForce hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5|small]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5|small] [--dump-outputs DIR] [--full]
 
 A "step" is ONE force evaluation (direct-space sliced pair loop + exclusion/1-4 lists + sliced PME reciprocal
 pipeline) of the synthetic periodic box named by BASELINE.json (default c3: 300k atoms, 4 subsets with lambda
@@ -12,9 +12,15 @@ N > 1 (launched by torch.distributed.run): ONE system, strong scaling -- PME sub
 work items are sharded over the ranks (snb_config.shard_rank/shard_count) and the per-rank partial forces are
 summed with one RCCL all-reduce per step.
 
-Extra objects on the JSON line: "roofline" for the dominant kernel (the direct-space tile kernel, timed with HIP
-events on the engine's own stream; algorithmic bytes 52*N + 1792*T) and "cpu_baseline" (the CPU
-oracle timed on a bounded, down-scaled sample of the same workload, rank 0 / N=1 only).
+A plain run sets up, warms up with W steps of the kind `value` quotes, times exactly K of them and prints the JSON line.
+Its "roofline" objects come from the kernel stamps of those K steps (the direct-space tile kernel and the PME kernels,
+timed with HIP events on the engine's own stream; algorithmic bytes 52*N + 1792*T).
+--dump-outputs DIR: after the timed steps, what the last of them computed -- forces.npy ([N, 3] in user atom order, float32,
+or float64 in double precision) and, when the step carries derivatives, derivative_slice_energies.npy (the raw energies of
+the derivative slices, float64) -- from inputs that are the same in every run with the same arguments.
+--full: everything else, as before -- the other step kind's K steps, the exchange alone and the unsharded engine (N > 1),
+resident coordinates, one energy step, displacement-triggered rebuilds, "cpu_baseline" (the CPU oracle on the same
+workload, rank 0 / N=1 only) and the double-precision leg with its parity sample (--no-* switches drop single legs).
 """
 import argparse
 import ctypes
@@ -296,6 +302,33 @@ class Engine:
     def sync(self): self.ok(self.L.snb_synchronize(self.h))
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # the largest config (c5, 10^6 atoms in double precision) dumps 24 MB
+
+
+def dump_outputs(out_dir, eng, forces, derivatives, deriv_slices, S, world, dist, rank):
+    """--dump-outputs: what the last timed step computed, as its caller receives it -- forces.npy ([N, 3], user atom order, float32 or float64
+    as the engine's precision; summed over the ranks when N > 1) and, for a step with derivatives, derivative_slice_energies.npy ([k, 2]
+    float64: the raw (Coulomb, vdW) energies of the k derivative slices, i.e. dE/dlambda of the scaling parameters bound to them, summed
+    over the ranks; the energies of the other slices are unspecified after such a step, include/snb.h).  Every rank takes part, rank 0
+    writes.  Returns {name: [shape, dtype]} on rank 0."""
+    import torch
+    arrays = {"forces": forces.cpu().numpy()}
+    if derivatives:
+        se = eng.slice_energies(S)
+        if world > 1:
+            t = torch.tensor(se, device=forces.device)
+            dist.all_reduce(t)
+            se = t.cpu().numpy()
+        arrays["derivative_slice_energies"] = np.ascontiguousarray(se[deriv_slices != 0])
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES, "outputs exceed the dump limit"
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: [list(a.shape), str(a.dtype)] for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -305,12 +338,16 @@ def main():
     ap.add_argument("--padding", type=float, default=0.1, help="neighbour-list skin in nm")
     ap.add_argument("--rebuild-interval", type=int, default=20, help="re-sort atoms and rebuild the tile lists every this many steps (inside the timed region)")
     ap.add_argument("--precision", default=None, choices=["single", "mixed", "double"], help="override the config's precision (mixed: single-precision arithmetic, 64-bit fixed-point force accumulation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-auto-leg", action="store_true", help="skip the leg with displacement-triggered rebuilds (the `displacement_triggered_rebuilds` object of the JSON line)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure (the legs below, the other step kind, resident coordinates, an energy step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-auto-leg", action="store_true", help="--full: skip the leg with displacement-triggered rebuilds (the `displacement_triggered_rebuilds` object of the JSON line)")
     ap.add_argument("--no-balance", action="store_true", help="N > 1: keep the even i-block split instead of balancing direct-space work against the ranks' reciprocal work")
     ap.add_argument("--check", action="store_true", help="also compare forces/energies with the CPU oracle (slow at full size)")
-    ap.add_argument("--no-double", action="store_true", help="skip the double-precision leg (the `double_precision` object of the JSON line)")
+    ap.add_argument("--no-double", action="store_true", help="--full: skip the double-precision leg (the `double_precision` object of the JSON line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # --gpus N > 1 without a launcher: start the N ranks ourselves (torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1)
     # BEFORE anything in this process touches the GPU, relay rank 0's JSON line and exit with the launcher's code.  Never fall through to a
@@ -385,6 +422,12 @@ def main():
         if world > 1:
             dist.all_reduce(forces)          # RCCL, ordered after the engine's kernels on the same stream
 
+    # `value` is the step kind the config names (c3 family: with derivatives; the others: forces only).  Derivatives are requested for the
+    # scaling parameters of the workload: the slices whose lambda differs from 1
+    headline_deriv = cfg_name in DERIVATIVE_CONFIGS
+    S = nsub * (nsub + 1) // 2
+    deriv_slices = (np.abs(w["lam"] - 1.0).max(axis=1) > 0).astype(np.int32)
+    eng.set_energy_slices(deriv_slices)
     t_rebuild0 = time.perf_counter()
     fenced_step(0); eng.sync()
     first_ms = (time.perf_counter() - t_rebuild0) * 1e3
@@ -411,23 +454,21 @@ def main():
             eng.set_shard_blocks(block_ranges[rank][0], block_ranges[rank][1], period)
     # Untimed pre-conditioning before the W warm-up steps: a fresh process starts with the GPU at idle clocks (kernel stamps of the first
     # ~100 ms read 15 % long: 0.239 ms for the pair kernel against 0.204 sustained) and with list buffers that still grow at the first few
-    # rebuilds; 250 steps (13 rebuilds, ~0.12 s) bring both to their steady state.  Then W warm-up steps, then exactly K timed steps.
+    # rebuilds; 250 steps (13 rebuilds, ~0.12 s) bring both to their steady state.  Then W warm-up steps, then exactly K timed steps, all of
+    # the step kind the timed steps run.
     # (250 steps before the timed region, not 240: with a rebuild every 20 steps the region would otherwise START with a rebuild, issued into
     # a GPU the synchronisation in front of the region has just drained -- a host-bound millisecond at idle clocks that a long run pays once
     # and a 20-step region pays in full: measured 1.7 ms per region on c4, 0.2 ms on c3.  Now the region's rebuilds fall mid-region, with the
     # queue full, as every rebuild of a long run does; their number per 20 steps is unchanged.)
     precondition = max(0, 250 - args.warmup) if not os.environ.get("SNB_BENCH_NO_PRECONDITION") else 0
     for i in range(precondition):
-        fenced_step(1 << 20 | i)
+        fenced_step(1 << 20 | i, derivatives=headline_deriv)
     for i in range(1, args.warmup + 1):
-        fenced_step(i)
+        fenced_step(i, derivatives=headline_deriv)
     eng.sync(); torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     eng.set_timing_interval(int(os.environ.get("SNB_BENCH_TIMING_INTERVAL", max(1, min(32, (args.steps + 2) // 3)))))      # >= 3 timed (eager, serial) steps with kernel stamps even in a short region (an eager stamped step costs ~85 us more than a replayed, overlapped one)
-    # derivatives are requested for the scaling parameters of the workload: the slices whose lambda differs from 1
-    deriv_slices = (np.abs(w["lam"] - 1.0).max(axis=1) > 0).astype(np.int32)
-    eng.set_energy_slices(deriv_slices)
 
     def timed_region(first, derivatives):
         """EXACTLY K steps bracketed by barrier + synchronize on both sides; MAX over ranks.  Returns (ms per step, engine stats of the region)."""
@@ -452,23 +493,24 @@ def main():
         stx = eng.stats()
         return elapsed * 1e3 / args.steps, stx, int(stx.n_rebuilds) - before
 
-    # Two regions of K steps each, same walk, same rebuild cadence:
+    # Two step kinds, each timed as a region of K steps (same walk, same rebuild cadence):
     #  * forces only -- snb_execute(include_energy = 0);
     #  * the step BASELINE.json config 3 names, "with lambda_elec / lambda_vdW derivatives": a force that requests energy-parameter derivatives
     #    accumulates the raw per-slice energies on EVERY step (the reference does, CommonNonbondedSlicingKernels.cpp:712-718); the sums stay on
     #    the device (read once at the end, outside the region).
-    # `value` is the region the config names (c3 family: derivatives; the others: forces only); the other one is reported beside it.
-    plain_ms, st, rebuilds_plain = timed_region(args.warmup + 1, False)
-    for i in range(4):
-        fenced_step(args.warmup + args.steps + 1 + i, derivatives=True)
-    deriv_ms, st_d, rebuilds_deriv = timed_region(args.warmup + args.steps + 5, True)
-    headline_deriv = cfg_name in DERIVATIVE_CONFIGS
-    ms_per_step = deriv_ms if headline_deriv else plain_ms
-    st_head = st_d if headline_deriv else st
-    rebuilds_in_region = rebuilds_deriv if headline_deriv else rebuilds_plain
+    # The region of the kind `value` quotes comes first; --full times the other kind after it and reports it beside `value`.
+    ms_per_step, st_head, rebuilds_in_region = timed_region(args.warmup + 1, headline_deriv)
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, eng, forces, headline_deriv, deriv_slices, S, world, dist, rank)
+    other_ms = st_other = None
+    if args.full:
+        for i in range(4):
+            fenced_step(args.warmup + args.steps + 1 + i, derivatives=not headline_deriv)
+        other_ms, st_other, _ = timed_region(args.warmup + args.steps + 5, not headline_deriv)
+    plain_ms, deriv_ms = (other_ms, ms_per_step) if headline_deriv else (ms_per_step, other_ms)
     resident_ms = None
     allreduce_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         # the exchange alone: K all-reduces of the force array back to back (its share of ms_per_step, for the record)
         torch.cuda.synchronize(); dist.barrier()
         ta = time.perf_counter()
@@ -478,7 +520,7 @@ def main():
         allreduce_ms = (time.perf_counter() - ta) * 1e3 / args.steps
     overruns = int(eng.stats().n_list_overruns)
     one_gpu_same = None; world_facts = None
-    if world > 1:
+    if world > 1 and args.full:
         # The curve's own anchor, measured in THIS run: rank 0 runs the UNSHARDED engine of the same workload, the same
         # step kind (the one `value` quotes), walk and rebuild cadence for K steps on its GPU while the other ranks wait at the barrier.
         if rank == 0:
@@ -510,7 +552,7 @@ def main():
         dist.all_gather_object(every, mine)
         world_facts = {"world_size": int(dist.get_world_size()), "backend": str(dist.get_backend()), "ranks": every,
                        "distinct_devices": len({(r_["host"], r_["device_index"]) for r_ in every})}
-    if world == 1:
+    if world == 1 and args.full:
         # For the record (never `value`): the same evaluations fed from two coordinate sets generated beforehand, i.e. nothing but
         # force evaluations on the stream.  The coordinate-update kernel of the main region stands where an integrator would.
         ring = [pos0 + 0.5 * walk[j] for j in (1, 2)]
@@ -612,34 +654,34 @@ def main():
         return rows
 
     nheld = len([s_ for s_ in range(nsub) if s_ % world == rank]) if world > 1 else nsub
-    roof_plain = pair_roofline(st, False)
-    roof_deriv = pair_roofline(st_d, True)
-    roof = roof_deriv if headline_deriv else roof_plain
+    roof = pair_roofline(st_head, headline_deriv)
     direct_ms = st_head.sum_direct_ms / max(st_head.n_timed, 1)
     recip_ms = st_head.sum_recip_ms / max(st_head.n_timed, 1)
     gpu_ms = st_head.sum_total_ms / max(st_head.n_timed, 1)
 
-    # one energy evaluation for the record (per-slice energies)
-    eng.rebuild()
-    eng.set_positions_device(pos0.data_ptr(), is_double)
-    torch.cuda.synchronize()
-    energy_ms = 1e30
-    for _ in range(4):      # best of four: the first may coincide with a scheduled list rebuild
-        t1 = time.perf_counter(); e_total = eng.execute(True); eng.sync(); energy_ms = min(energy_ms, (time.perf_counter() - t1) * 1e3)
+    energy_ms = energy_gpu_ms = None
+    if args.full:
+        # one energy evaluation for the record (per-slice energies)
+        eng.rebuild()
+        eng.set_positions_device(pos0.data_ptr(), is_double)
+        torch.cuda.synchronize()
+        energy_ms = 1e30
+        for _ in range(4):      # best of four: the first may coincide with a scheduled list rebuild
+            t1 = time.perf_counter(); e_total = eng.execute(True); eng.sync(); energy_ms = min(energy_ms, (time.perf_counter() - t1) * 1e3)
+        energy_gpu_ms = eng.stats().last_total_ms
     out = {
         "metric": "ns/day (force evaluation only, dt = 2 fs)", "value": round(ns_day, 3), "unit": "ns/day", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "f64" if is_double else "f32", "data": "synthetic",
         "value_step": "with lambda derivatives (snb_execute include_energy = 2 every step)" if headline_deriv else "forces only",
-        "value_forces_only": round(86.4 * 2.0 / plain_ms, 3), "ms_per_step_forces_only": round(plain_ms, 4),
-        "value_with_derivatives": round(86.4 * 2.0 / deriv_ms, 3), "ms_per_step_with_derivatives": round(deriv_ms, 4),
         "config": {"workload": ("%s: %d-atom " + ("triclinic cell a=(L,0,0) b=(L/3,L,0) c=(-L/4,L/4,L)" if "box" in w else "cubic box") + " L=%.3f nm, %d subsets, %s %d^3%s, cutoff 1.0 nm, alpha 2.6283/nm, %d exclusions, list skin %.2f nm")
-                   % (cfg_name, N, Lbox, nsub, "PME" if method == 4 else "LJPME", st.grid[0], (" + dispersion %d^3" % st.dgrid[0]) if method == 5 else "",
+                   % (cfg_name, N, Lbox, nsub, "PME" if method == 4 else "LJPME", st_head.grid[0], (" + dispersion %d^3" % st_head.dgrid[0]) if method == 5 else "",
                       len(w["exc_qq"]), args.padding),
-                   "tiles_32x32": T, "blocks": int(st.n_blocks), "rebuild_interval": args.rebuild_interval, "rebuilds_in_timed_region": rebuilds_in_region, "host_rebuilds": int(st.n_host_rebuilds), "neighbor_rebuild_ms": round(st.last_rebuild_ms, 2),
+                   "tiles_32x32": T, "blocks": int(st_head.n_blocks), "rebuild_interval": args.rebuild_interval, "rebuilds_in_timed_region": rebuilds_in_region, "host_rebuilds": int(st_head.n_host_rebuilds), "neighbor_rebuild_ms": round(st_head.last_rebuild_ms, 2),
                    "ms_per_step_resident_coordinates": round(resident_ms, 4) if resident_ms is not None else None,
                    "derivative_slices": [int(i) for i in np.nonzero(deriv_slices)[0]], "list_overruns": overruns, "preconditioning_steps": precondition, "allreduce_ms": round(allreduce_ms, 4) if allreduce_ms is not None else None,
-                   "first_call_ms": round(first_ms, 1), "energy_step_ms": round(energy_ms, 3), "energy_step_gpu_ms": round(eng.stats().last_total_ms, 3),
+                   "first_call_ms": round(first_ms, 1), "energy_step_ms": round(energy_ms, 3) if energy_ms is not None else None,
+                   "energy_step_gpu_ms": round(energy_gpu_ms, 3) if energy_gpu_ms is not None else None,
                    "gpu_ms_per_step": round(gpu_ms, 4), "direct_kernel_ms": round(direct_ms, 4), "reciprocal_ms": round(recip_ms, 4),
                    # replayed steps run the PME chain beside a CU-limited resident launch of the pair kernel (engine.hip overlapMode; the eager stamped
                    # steps behind `roofline` stay serial, so every kernel is still timed alone): the engine's own rule, restated
@@ -648,9 +690,15 @@ def main():
                    "rebuild_beside_steps": os.environ.get("SNB_SIDE_REBUILD", "1") != "0" and args.rebuild_interval > int(os.environ.get("SNB_SIDE_LEAD", "3")) + 1 and args.padding > 0,
                    "parallelism": ("subset-grid + i-block sharding x%d, RCCL all-reduce of forces" % world) if world > 1 else "1 GPU"},
         "roofline": roof,
-        "roofline_other_step": roof_plain if headline_deriv else roof_deriv,
         "roofline_pme": pme_rooflines(st_head, nheld),
     }
+    for kind, ms_ in (("forces_only", plain_ms), ("with_derivatives", deriv_ms)):
+        if ms_ is not None:
+            out["value_" + kind] = round(86.4 * 2.0 / ms_, 3); out["ms_per_step_" + kind] = round(ms_, 4)
+    if st_other is not None:
+        out["roofline_other_step"] = pair_roofline(st_other, not headline_deriv)
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dumped
     # HBM-side traffic of the pair kernel: PMC passes cannot run inside this process (rocprofv3 --pmc wraps the whole command, in separate
     # FETCH_SIZE / WRITE_SIZE passes: tools/pmc_hbm.sh).  `traffic` therefore stays null here; the figure of the committed profile of this
     # command is quoted under its own key, with the tile count it was taken at.
@@ -667,10 +715,10 @@ def main():
             break
     if block_ranges is not None:
         out["config"]["i_block_ranges_of_128"] = [list(r) for r in block_ranges]
-    if world > 1:
+    if world > 1 and args.full:
         out["one_gpu_same_workload"] = one_gpu_same
         out["distributed"] = world_facts
-    if rank == 0 and world == 1 and not args.no_auto_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_auto_leg:
         # For the record (never `value`): the same workload, walk and step kind with DISPLACEMENT-TRIGGERED rebuilds (rebuild_interval < 0: the mode
         # the plugin adapter of INTEGRATION.md runs the engine in -- the reference relies on OpenMM's padded list doing the same).  These rebuilds
         # run in line.
@@ -696,7 +744,7 @@ def main():
                                                   "list_overruns": int(st2.n_list_overruns), "padded_atoms": int(st2.n_padded_atoms), "step": "with derivatives" if headline_deriv else "forces only",
                                                   "note": "snb_config.rebuild_interval = -100: rebuild when an atom has moved 0.8 * skin / 2; same atoms, walk and step kind as `value`"}
         e2.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # The CPU oracle on the FULL workload (round 4: its pair list and pair loops are threaded, one evaluation of c3 takes seconds, so
         # nothing is scaled any more): one evaluation to size the sample, then as many as fit ~20 s, at least 2, at most 6.
         import oracle as _o
@@ -716,7 +764,7 @@ def main():
         ws["pos"] = np.ascontiguousarray(ws["pos"].astype(np.float32).astype(np.float64))      # float-representable coordinates: the oracle and engines of either precision see identical inputs
         ms24, ds24 = (4 if method == 4 else 5), (27 if method == 5 else 0)
         fo_s, so_s, _, _ = oracle_eval(ws, ms24, 54, ds24)
-    if rank == 0 and world == 1 and not args.no_double and not is_double:
+    if args.full and rank == 0 and world == 1 and not args.no_double and not is_double:
         # north_star couples the roofline target with "per-slice energies to 1e-5", which only double precision delivers: the same workload in
         # SNB_DOUBLE beside the headline (its own K-step regions, same walk and cadence), the pair kernel against the double-precision byte
         # model (76 N + 2560 T), and the worst slice-energy / force error of both precisions against the oracle on the 24k-atom sample.

@@ -1,11 +1,12 @@
-"""Copies the judged artefacts of a round from gpurun_out/ (scratch) into profiles/ (tracked):
-    tools/final_profiles.sh  -> gpurun_out/final/{bench.json, kernel_stats.csv, pmc_sq.txt}
-    tools/pmc_hbm.sh hb_rNN  -> gpurun_out/hb_rNN_hbm.json   (FETCH_SIZE / WRITE_SIZE per kernel, separate --pmc passes)
+"""Copies the judged artefacts of a round from $OUT (scratch, default tools_out/) into profiles/ (tracked):
+    tools/final_profiles.sh  -> $OUT/final/{bench.json, kernel_stats.csv, pmc_sq.txt}
+    tools/pmc_hbm.sh hb_rNN  -> $OUT/hb_rNN_hbm.json   (FETCH_SIZE / WRITE_SIZE per kernel, separate --pmc passes)
 usage: python tools/make_profiles.py r02 [config]"""
 import json, os, shutil, sys
 tag = sys.argv[1]; cfg = sys.argv[2] if len(sys.argv) > 2 else "c3"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "gpurun_out", "final"); dst = os.path.join(root, "profiles")
+scratch = os.path.join(root, os.environ.get("OUT", "tools_out"))
+src = os.path.join(scratch, "final"); dst = os.path.join(root, "profiles")
 shutil.copy(os.path.join(src, "bench.json"), os.path.join(dst, "%s_%s_default_bench.json" % (tag, cfg)))
 shutil.copy(os.path.join(src, "kernel_stats.csv"), os.path.join(dst, "%s_%s_default_bench_kernel_stats.csv" % (tag, cfg)))
 shutil.copy(os.path.join(src, "pmc_sq.txt"), os.path.join(dst, "%s_%s_pmc_sq.txt" % (tag, cfg)))
@@ -15,7 +16,7 @@ for extra, name in (("bench_serial.json", "serial_bench.json"), ("kernel_stats_o
 if os.path.exists(os.path.join(src, "pmc_mfma.txt")):
     shutil.copy(os.path.join(src, "pmc_mfma.txt"), os.path.join(dst, "%s_%s_pmc_mfma.txt" % (tag, cfg)))
 bench = json.loads(open(os.path.join(src, "bench.json")).read().strip().splitlines()[-1])
-hb = json.load(open(os.path.join(root, "gpurun_out", "hb_%s_hbm.json" % tag)))
+hb = json.load(open(os.path.join(scratch, "hb_%s_hbm.json" % tag)))
 def pick(deriv):
     want = "true, true, false, false" if deriv else "true, false, false, false"
     names = [k for k in hb if ("k_directPacked" in k and want in k) or "k_direct<double" in k]
