@@ -1019,13 +1019,22 @@ public:
     // GPU neighbour build (neighbor.hip): rectangular periodic boxes with cutoff.  Returns false when the
     // host builder must take over (per-pair-wrap regime, gather-capacity overflow).
     // ------------------------------------------------------------------------------------------
-    // the totals of a build through mapped host memory: spins on the sequence number k_nbPublish writes last (falls back to a copy after 2 s)
-    void waitForTotals(int seq, int* h) {
-        const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(2);
+    // the totals of a build through mapped host memory: spins on the sequence number k_nbPublish writes last (falls back to a copy after
+    // SNB_NB_PUBLISH_WAIT_MS, default 2000).  The copy goes on `buildStream`, the stream the build was enqueued on, and waits for it: only
+    // there is it ordered after the build's counters (a side build writes them on streamBuild, not on the live step stream)
+    void waitForTotals(int seq, int* h, hipStream_t buildStream) {
+        static const int waitMs = getenv("SNB_NB_PUBLISH_WAIT_MS") ? std::max(0, atoi(getenv("SNB_NB_PUBLISH_WAIT_MS"))) : 2000;      // test switch (0: always the copy)
         volatile int* pub = hNbPub;
-        while (pub[8] != seq && std::chrono::steady_clock::now() < deadline) { __builtin_ia32_pause(); }
-        if (pub[8] == seq) { for (int k = 0; k < 8; k++) h[k] = pub[k]; }
-        else { HIPCHECK(hipMemcpyAsync(h, dCounters.p, sizeof(int) * 8, hipMemcpyDeviceToHost, stream)); HIPCHECK(hipStreamSynchronize(stream)); }
+        if (waitMs > 0) {
+            const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(waitMs);
+            while (pub[8] != seq && std::chrono::steady_clock::now() < deadline) { __builtin_ia32_pause(); }
+            if (pub[8] == seq) { for (int k = 0; k < 8; k++) h[k] = pub[k]; return; }
+        }
+        HIPCHECK(hipMemcpyAsync(h, dCounters.p, sizeof(int) * 8, hipMemcpyDeviceToHost, buildStream));
+        HIPCHECK(hipStreamSynchronize(buildStream));
+        static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
+        if (verbose) fprintf(stderr, "[snb] totals of build %d not published within %d ms: copied on the %s stream (tiles %d, work items %d + %d, overflow %d, padded %d)\n",
+                             seq, waitMs, buildStream == streamBuild ? "side-build" : "build", h[0], h[1], h[4], h[3], h[7]);
     }
     // a build whose totals are in: host-side counts, the next prediction, statistics
     void acceptBuild(const int* h, float sortMs) {
@@ -1093,6 +1102,7 @@ public:
         sideBuilding = false; stream = liveStream; devUserPos = livePos; swapListSets();
         if (!ok) { colCells[0] = liveCells[0]; colCells[1] = liveCells[1]; HIPCHECK(hipEventSynchronize(evBuilt)); }      // (whatever was enqueued has finished with the scratch arrays)
         sidePending = ok;
+        { static const bool verbose = getenv("SNB_VERBOSE") != nullptr; if (verbose && ok) fprintf(stderr, "[snb] side build started after execute %lld\n", stepCounter - 1); }
     }
     // drops a pending side build (its result will not be used): waits until it has finished with the scratch arrays
     void cancelSideBuild() {
@@ -1105,7 +1115,7 @@ public:
     bool finishSideBuild() {
         sidePending = false;
         int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        waitForTotals(sideSeq, h);
+        waitForTotals(sideSeq, h, streamBuild);      // (a fallback copy must wait for the side build, not for the live steps)
         HIPCHECK(hipEventSynchronize(evBuilt));      // (returns at once: the totals are the build's last kernel but one)
         static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
         static const bool reject = getenv("SNB_SIDE_REJECT") != nullptr;      // test switch: every side build is discarded and the rebuild repeated in line
@@ -1123,6 +1133,7 @@ public:
         launchDispFlagsReset(dDispFlags, stream);      // (in stream order: steps on the old list may still be queued, and their flags belong to it)
         HIPCHECK(hipEventRecord(evFlagsReset, stream)); flagsResetPending = true;      // (until then the host copy still shows the old list's flags)
         sideBuilds++;
+        if (verbose) fprintf(stderr, "[snb] side-built list in use from execute %lld\n", stepCounter);
         return true;
     }
 
@@ -1290,7 +1301,7 @@ public:
             if (hNbPub && dNbPub && !noSpin) {
                 const int seq = ++nbPubSeq;
                 launchNeighborPublish(dCounters.p, dNbPub, seq, stream);
-                waitForTotals(seq, h);
+                waitForTotals(seq, h, stream);
                 HIPCHECK(hipStreamSynchronize(stream));      // (the events below are read next; nothing is running any more)
             } else {
                 HIPCHECK(hipMemcpyAsync(h, dCounters.p, sizeof(h), hipMemcpyDeviceToHost, stream));
