@@ -178,7 +178,15 @@ snb_status snb_rebuild_neighbors(snb_handle h);             /* force a tile rebu
  * CommonNonbondedSlicingKernels.cpp:712-718) and summed ON THE DEVICE as the step's last kernel.  With energy == NULL nothing is read
  * back and nothing synchronises -- such a step replays a captured graph like a forces-only one; snb_get_slice_energies fetches the
  * sums when the caller needs them.  With energy != NULL it receives sum_slices lambda*E (this synchronises the stream).
- * include_energy == 2: a derivative-only step -- as 1, restricted to the slices of snb_set_energy_slices (energy must be NULL). */
+ * include_energy == 2: a derivative-only step -- as 1, restricted to the slices of snb_set_energy_slices (energy must be NULL).
+ * include_forces == 0 with include_energy 1 or 2: an ENERGY-ONLY step (OpenMM getState(getEnergy=True) without forces, a barostat trial,
+ * re-evaluating a stored frame for MBAR: E(lambda) = sum_s lambda_s E_s).  Mode 1 produces the total and every raw slice energy, mode 2 the
+ * slices of snb_set_energy_slices (energy must be NULL).  It evaluates no forces: snb_get_forces still returns the forces of the last forces
+ * step (when the step rebuilds the lists -- which re-sorts the atoms -- the engine first keeps a copy of those forces and serves it until the
+ * next forces step), and the buffer of snb_set_force_output is not touched, whatever its accumulate flag.  It follows the neighbour-list
+ * rules of any execute (box-change and displacement rebuilds, the fixed-interval count, side builds) and runs as plain launches: it never
+ * captures or updates a step graph itself, while a rebuild it performs marks the graphs stale as any rebuild does (the next forces step
+ * refreshes its graph).  include_forces == 0 with include_energy == 0: nothing is enqueued (SNB_OK). */
 snb_status snb_execute(snb_handle h, int32_t include_forces, int32_t include_energy, int32_t include_direct,
                        int32_t include_reciprocal, double* energy);
 /* out: [N][3] in the type selected by is_double; accumulate != 0 adds to what is there (the reference

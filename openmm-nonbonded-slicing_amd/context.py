@@ -166,6 +166,7 @@ class HipCalcSlicedNonbondedForceKernel:
         for (sl, _t), (_name, hasDeriv) in self._binding.items():
             if hasDeriv:
                 mask[sl] = 1
+        self._derivMask = mask
         self._check(self._lib.snb_set_energy_slices(self._h, _ip(mask)))
 
     def _effective(self, params):
@@ -229,14 +230,17 @@ class HipCalcSlicedNonbondedForceKernel:
             self._check(self._lib.snb_set_lambdas(self._h, _dp(np.ascontiguousarray(lam))))
             self._lastLambdas = lam
 
-    # -- CalcSlicedNonbondedForceKernel::execute (NonbondedSlicingKernels.h:59) ---------------------
-    def execute(self, context, includeForces, includeEnergy, includeDirect, includeReciprocal):
-        params = context.getParameters()
-        self._push_parameters(params)
+    def _push_state(self, context):
+        self._push_parameters(context.getParameters())
         box = np.ascontiguousarray(context.getPeriodicBoxVectors(), dtype=np.float64).reshape(9)
         self._check(self._lib.snb_set_box(self._h, _dp(box)))
         pos = context._positions
         self._check(self._lib.snb_set_positions(self._h, pos.ctypes.data_as(ctypes.c_void_p), 0, 1, 0))
+
+    # -- CalcSlicedNonbondedForceKernel::execute (NonbondedSlicingKernels.h:59) ---------------------
+    # (includeForces false: an energy-only step -- the engine evaluates no forces and keeps those of the last forces step; nothing is read back)
+    def execute(self, context, includeForces, includeEnergy, includeDirect, includeReciprocal):
+        self._push_state(context)
         energy = ctypes.c_double(0.0)
         wantE = bool(includeEnergy) or bool(self._derivNames)
         # Q4: derivatives accumulate whether or not the energy is requested -- then only the slices they are bound to are evaluated (mode 2)
@@ -253,6 +257,28 @@ class HipCalcSlicedNonbondedForceKernel:
                 if hasDeriv:
                     context._energyParamDerivs[name] = context._energyParamDerivs.get(name, 0.0) + sl[s, t]
         return energy.value if includeEnergy else 0.0
+
+    def computeSliceEnergies(self, context, slices=None):
+        """Raw per-slice energies [S][2] (Coulomb, vdW) at the context's positions and box, from one energy-only step (include_forces = 0).
+        The energy of any lambda state is their linear combination, E(lambda) = sum_s lambda_s . E_s: the per-frame call of an MBAR or
+        reweighting pass.  slices: indices of the slices wanted -- only those are evaluated (include_energy = 2), the other rows are NaN;
+        None: every slice.  The forces of the last forces step stay where they are."""
+        self._push_state(context)
+        if slices is None:
+            self._check(self._lib.snb_execute(self._h, 0, 1, 1, 1, None))
+        else:
+            mask = np.zeros(self.numSlices, dtype=np.int32)
+            mask[np.asarray(list(slices), dtype=np.int64)] = 1
+            self._check(self._lib.snb_set_energy_slices(self._h, _ip(mask)))
+            try:
+                self._check(self._lib.snb_execute(self._h, 0, 2, 1, 1, None))
+            finally:      # (the derivative-only steps of execute() keep their own mask)
+                self._check(self._lib.snb_set_energy_slices(self._h, _ip(self._derivMask)))
+        sl = np.zeros((self.numSlices, 2))
+        self._check(self._lib.snb_get_slice_energies(self._h, _dp(sl)))
+        if slices is not None:
+            sl[mask == 0] = np.nan
+        return sl
 
     # -- CalcSlicedNonbondedForceKernel::copyParametersToContext (NonbondedSlicingKernels.h:66) ------
     def copyParametersToContext(self, context, force):

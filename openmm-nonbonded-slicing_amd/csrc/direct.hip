@@ -181,7 +181,8 @@ __device__ inline double rowRor1(double v) {
 // The 16 pair steps of one tile for this lane's row.  MASKED: the tile carries an exclusion/padding mask;
 // SWITCH: LJ switching function active.  Both are wave-uniform and resolved at compile time so that the common
 // case (no mask, no switch) carries no test for them in the loop.
-template <typename Real, int MC, bool WRAP, bool ENERGY, bool MASKED, bool SWITCH>
+// FORCES == false (energy-only tile kernel, ENERGY == true): the energies alone -- no force accumulation, so the force arithmetic is dead code.
+template <typename Real, int MC, bool WRAP, bool ENERGY, bool MASKED, bool SWITCH, bool FORCES = true>
 __device__ __forceinline__ void tileSteps(const DirectParams<Real>& p, const typename Vec<Real>::T4* rdPos, const typename Vec<Real>::T2* rdSe,
                                           const typename Vec<Real>::T4 pi, const typename Vec<Real>::T2 sei, const Real qi, const Real qiS, const Real epsiS,
                                           const Real c6i, const Real lamC, const Real lamL, const unsigned maskWord, const int c,
@@ -274,14 +275,16 @@ __device__ __forceinline__ void tileSteps(const DirectParams<Real>& p, const typ
                 fC = qq * invR;                                               // (:611)
                 if (ENERGY) eC = fC;
             }
+            if (ENERGY) { ecl += include ? eC : Real(0); elj += include ? eLJ : Real(0); }
+            if constexpr (FORCES) {
             Real f = ENERGY ? (lamL * fLJ + lamC * fC) : (fLJ + fC);
             f *= invR * invR;
             f = include ? f : Real(0);
-            if (ENERGY) { ecl += include ? eC : Real(0); elj += include ? eLJ : Real(0); }
             const Real gx = f * dx, gy = f * dy, gz = f * dz;
             fix += gx; fiy += gy; fiz += gz;
             // the accumulator follows its j-slot along the row: rotate in (slot of lane c at step s = slot of lane c-1 at step s-1), then add
             fjx = rowRor1(fjx) - gx; fjy = rowRor1(fjy) - gy; fjz = rowRor1(fjz) - gz;
+            }
         }
 }
 
@@ -299,8 +302,9 @@ __device__ inline float rowRor8(float v) { return __builtin_bit_cast(float, __bu
 // travels WITH the j-slot by a one-lane DPP row rotation per step (v_add_f32_dpp: one VALU op per component, no LDS),
 // so after 16 steps lane c holds the force on j-slot c.  j-atom data is read from LDS (staged once per tile, each
 // 16-atom half stored twice so the rotated index c+16-s needs no wrap).
-template <typename Real, bool ENERGY> __device__ __forceinline__ void exceptionsBody(const PairListParams<Real>& p, const int blk);
-template <typename Real, bool ENERGY> __device__ __forceinline__ void exclusionAtomsBody(const PairListParams<Real>& p, const int blk);
+// (FORCES == false: the energy-only list bodies of include_forces == 0 steps -- slice energies alone, no force update)
+template <typename Real, bool ENERGY, bool FORCES = true> __device__ __forceinline__ void exceptionsBody(const PairListParams<Real>& p, const int blk);
+template <typename Real, bool ENERGY, bool FORCES = true> __device__ __forceinline__ void exclusionAtomsBody(const PairListParams<Real>& p, const int blk);
 // (as in k_directPacked: the first nListBlocks work-groups of the launch run the O(N) pair lists -- exclusion corrections, then 1-4
 // exceptions -- so that their latency-bound work overlaps the tile work instead of trailing it as a 65 us launch of its own on c5)
 template <typename Real, int MC, bool WRAP, bool ENERGY>
@@ -457,7 +461,7 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 8 ? SNB_DIRECT_F64_WAVES : 4)
 // energy of the method (Ewald: qq erfc(ar)/r with the A&S erfc) -- from the
 // RAW i-parameters qiRaw / epsiRaw, while the forces keep using the lambda-scaled ones.  This is the kernel of every step of a force
 // that asks for energy-parameter derivatives (the reference accumulates them whether or not the energy is requested, Q4).
-template <int MC, bool MASKED, bool POLY, bool ENERGY, bool SWITCH>
+template <int MC, bool MASKED, bool POLY, bool ENERGY, bool SWITCH, bool FORCES = true>      // FORCES == false: energies alone, as tileSteps
 __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, const float4* rdPos, const float2* rdSe, const v2f pix, const v2f piy, const v2f piz,
                                                 const v2f sigi, const v2f qiS, const v2f epsiS, const v2f qiRaw, const v2f epsiRaw, const v2f c6iRaw, const float lamL, const unsigned maskA, const unsigned maskB, const int c,
                                                 v2f& fix, v2f& fiy, v2f& fiz, float& fjx, float& fjy, float& fjz, v2f& ecl, v2f& elj) {
@@ -555,14 +559,13 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
             eC.x = inA ? eC.x : 0.0f; eC.y = inB ? eC.y : 0.0f; eLJ.x = inA ? eLJ.x : 0.0f; eLJ.y = inB ? eLJ.y : 0.0f;
             ecl = ecl + eC; elj = elj + eLJ;
         }
+        if constexpr (FORCES) {
         const v2f gx = f * dx, gy = f * dy, gz = f * dz;
         fix = fix + gx; fiy = fiy + gy; fiz = fiz + gz;
         fjx = rowRor1(fjx) - (gx.x + gx.y); fjy = rowRor1(fjy) - (gy.x + gy.y); fjz = rowRor1(fjz) - (gz.x + gz.y);
+        }
     }
 }
-
-template <typename Real, bool ENERGY> __device__ __forceinline__ void exceptionsBody(const PairListParams<Real>& p, const int blk);
-template <typename Real, bool ENERGY> __device__ __forceinline__ void exclusionAtomsBody(const PairListParams<Real>& p, const int blk);
 
 // The first nListBlocks work-groups of the launch run the O(N) pair lists (exclusion corrections, then 1-4 exceptions: latency-bound
 // work that overlaps the VALU-bound tile work instead of trailing it as a launch of its own); the others loop over tile work items.
@@ -727,6 +730,166 @@ __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<floa
     if (p.stepTrace && threadIdx.x == 0) p.stepTrace[p.traceSlot + 1] = (long long)wall_clock64();      // (plain store: the last work-group to leave writes last)
 }
 
+// ---- energy-only tile kernels (steps with include_forces == 0) ------------------------------------
+// The raw slice energies of the same work items and tiles, from the same lane layout and the same per-lane accumulation order as the
+// energy instantiations of k_direct / k_directPacked (so the sums agree with those of an energy step to rounding), with no force arithmetic,
+// no force accumulators and no force stores.  A tile whose slice is not wanted (p.sliceNeed; include_energy == 2) is skipped whole --
+// the decision is uniform per tile, so the wave never loads its atoms.  The first nListBlocks work-groups run the energy-only pair lists.
+// No software pipeline: these steps are few (reporters, barostat trials, re-analysis), the forces-step kernels stay as they are.
+template <typename Real, int MC, bool WRAP>
+__global__ __launch_bounds__(256, (sizeof(Real) == 8 ? SNB_DIRECT_F64_WAVES : 4)) void k_directEnergy(const DirectParams<Real> p, const PairListParams<Real> q, const int nExclBlocks, const int nListBlocks) {
+    if ((int)blockIdx.x < nListBlocks) {
+        if ((int)blockIdx.x < nExclBlocks) { PairListParams<Real> qe = q; qe.n = q.nExclAtoms; exclusionAtomsBody<Real, true, false>(qe, blockIdx.x); }
+        else exceptionsBody<Real, true, false>(q, blockIdx.x - nExclBlocks);
+        return;
+    }
+    const int tileBlock = (int)blockIdx.x - nListBlocks, nTileBlocks = gridDim.x - nListBlocks;
+    double* const sliceE = SNB_SLICE_E_PARTITION(p.sliceE, p.nsub * (p.nsub + 1));
+    using T4 = typename Vec<Real>::T4;
+    using T2 = typename Vec<Real>::T2;
+    __shared__ T4 s_pos[4][64];
+    __shared__ T2 s_se[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 15, row = lane >> 4;
+    const int il = 16 * (row & 1) + c, jh = row >> 1, stageJ = 16 * (lane >> 5) + c;      // (lane layout of k_direct)
+    T4* myPos = s_pos[wid];
+    T2* mySe = s_se[wid];
+    const T4* rdPos = myPos + 32 * jh + c + 16;
+    const T2* rdSe = mySe + 32 * jh + c + 16;
+    for (int item = tileBlock * 4 + wid; item < p.numWork; item += nTileBlocks * 4) {
+        const int4 wi = p.workItems[p.workStart + item * p.workStride];
+        const int I = __builtin_amdgcn_readfirstlane(wi.x);
+        const int tBegin = __builtin_amdgcn_readfirstlane(wi.y), tEnd = tBegin + __builtin_amdgcn_readfirstlane(wi.z);
+        const T4 pi = p.posq[I * 32 + il];
+        const T2 sei = p.sigeps[I * 32 + il];
+        const Real qi = pi.w * p.k4pe;
+        Real c6i = 0;
+        if (MC == MC_LJPME) c6i = Real(8) * sei.x * sei.x * sei.x * sei.y;
+        Real ecl = 0, elj = 0;
+        int curSlice = -1;
+        for (int t = tBegin; t < tEnd; t++) {
+            const int4 head = p.tileInfo[t];
+            const int slice = __builtin_amdgcn_readfirstlane(head.x & 0xFFFF), maskIdx = __builtin_amdgcn_readfirstlane(head.y);
+            if (slice != curSlice) {
+                if (curSlice >= 0) {
+                    const double a = waveSum((double)ecl), b = waveSum((double)elj);
+                    if (lane == 0) { atomicAdd(&sliceE[2 * curSlice], a); atomicAdd(&sliceE[2 * curSlice + 1], b); }
+                }
+                ecl = 0; elj = 0; curSlice = slice;
+            }
+            if (__builtin_amdgcn_readfirstlane(p.sliceNeed[slice]) == 0) continue;      // (uniform) slice not wanted: the whole tile is skipped
+            const int code = p.tileJ[t * 32 + stageJ];
+            T4 pj; T2 sej;
+            if (code != -1) {
+                const int idx = code & SNB_JIDX_MASK;
+                pj = p.posq[idx]; sej = p.sigeps[idx];
+                if (!WRAP) {
+                    const int sc = (code >> SNB_JSHIFT_BITS) & 127;
+                    const int kx = sc / 25, ky = (sc - 25 * kx) / 5, kz = sc - 25 * kx - 5 * ky;
+                    const Real ka = Real(kx - 2), kb = Real(ky - 2), kc = Real(kz - 2);
+                    pj.x += ka * p.box[0] + kb * p.box[3] + kc * p.box[6]; pj.y += kb * p.box[4] + kc * p.box[7]; pj.z += kc * p.box[8];
+                }
+            } else { pj.x = Real(3e9) + Real(1e6) * c; pj.y = Real(-5e9); pj.z = Real(7e9); pj.w = 0; sej.x = 0; sej.y = 0; }
+            const unsigned maskWord = (maskIdx >= 0 ? p.masks[maskIdx * 32 + il] : 0u) >> (16 * jh);
+            const Real lamC = p.lambdas[2 * slice], lamL = p.lambdas[2 * slice + 1];
+            __builtin_amdgcn_wave_barrier();
+            myPos[lane] = pj; mySe[lane] = sej;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            Real fix = 0, fiy = 0, fiz = 0, fjx = 0, fjy = 0, fjz = 0;      // (not touched: FORCES == false)
+#define SNB_TILE_E(M, SW) tileSteps<Real, MC, WRAP, true, M, SW, false>(p, rdPos, rdSe, pi, sei, qi, qi, sei.y, c6i, lamC, lamL, maskWord, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj)
+            if (p.useSwitch && MC != MC_LJPME && MC != MC_NOCUTOFF) { if (maskIdx >= 0) SNB_TILE_E(true, true); else SNB_TILE_E(false, true); }
+            else { if (maskIdx >= 0) SNB_TILE_E(true, false); else SNB_TILE_E(false, false); }
+#undef SNB_TILE_E
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (curSlice >= 0) {
+            const double a = waveSum((double)ecl), b = waveSum((double)elj);
+            if (lane == 0) { atomicAdd(&sliceE[2 * curSlice], a); atomicAdd(&sliceE[2 * curSlice + 1], b); }
+        }
+    }
+}
+
+// Packed single-precision form (the energy instantiation of k_directPacked without its forces): lane (row r, column c) holds i-atoms c and
+// c+16 and meets one j-slot of j-quarter r per step, 8 steps per tile, tileStepsPacked with FORCES == false.
+template <int MC, bool POLY, bool SWITCH>
+__global__ __launch_bounds__(256, 4) void k_directPackedEnergy(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
+    if ((int)blockIdx.x < nListBlocks) {
+        if ((int)blockIdx.x < nExclBlocks) { PairListParams<float> qe = q; qe.n = q.nExclAtoms; exclusionAtomsBody<float, true, false>(qe, blockIdx.x); }
+        else exceptionsBody<float, true, false>(q, blockIdx.x - nExclBlocks);
+        return;
+    }
+    const int tileBlock = (int)blockIdx.x - nListBlocks, nTileBlocks = gridDim.x - nListBlocks;
+    double* const sliceE = SNB_SLICE_E_PARTITION(p.sliceE, p.nsub * (p.nsub + 1));
+    __shared__ float4 s_pos[4][64];
+    __shared__ float2 s_se[4][64];
+    __shared__ float4 s_shift[128];      // lattice-image shift of every 7-bit image code, as in k_directPacked
+    if (threadIdx.x < 128) {
+        const int sc = threadIdx.x;
+        const int kx = sc / 25, ky = (sc - 25 * kx) / 5, kz = sc - 25 * kx - 5 * ky;
+        const float ka = float(kx - 2), kb = float(ky - 2), kc = float(kz - 2);
+        s_shift[sc] = sc < 125 ? make_float4(ka * p.box[0] + kb * p.box[3] + kc * p.box[6], kb * p.box[4] + kc * p.box[7], kc * p.box[8], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 15, row = lane >> 4;
+    const int stageJ = 8 * row + (c & 7);
+    float4* myPos = s_pos[wid];
+    float2* mySe = s_se[wid];
+    const float4* rdPos = myPos + 16 * row + (c & 7) + 8;
+    const float2* rdSe = mySe + 16 * row + (c & 7) + 8;
+    for (int item = tileBlock * 4 + wid; item < p.numWork; item += nTileBlocks * 4) {
+        const int4 wi = p.workItems[p.workStart + item * p.workStride];
+        const int I = __builtin_amdgcn_readfirstlane(wi.x);
+        const int tBegin = __builtin_amdgcn_readfirstlane(wi.y), tEnd = tBegin + __builtin_amdgcn_readfirstlane(wi.z);
+        const float4 pa = p.posq[I * 32 + c], pb = p.posq[I * 32 + 16 + c];
+        const float2 sa = p.sigeps[I * 32 + c], sb = p.sigeps[I * 32 + 16 + c];
+        const v2f pix = {pa.x, pb.x}, piy = {pa.y, pb.y}, piz = {pa.z, pb.z};
+        const v2f qi = {pa.w * p.k4pe, pb.w * p.k4pe}, sigi = {sa.x, sb.x}, epsi = {sa.y, sb.y};
+        const v2f c6i = {8.0f * sa.x * sa.x * sa.x * sa.y, 8.0f * sb.x * sb.x * sb.x * sb.y};
+        v2f ecl = {0.f, 0.f}, elj = {0.f, 0.f};
+        int curSlice = -1; bool curNeeded = false;
+        auto flushEnergy = [&]() {      // (as k_directPacked's: wave sum in double, one atomic per term)
+            if (curSlice >= 0) {
+                const double a = waveSum((double)ecl.x + (double)ecl.y), b = waveSum((double)elj.x + (double)elj.y);
+                if (lane == 0) { atomicAdd(&sliceE[2 * curSlice], a); atomicAdd(&sliceE[2 * curSlice + 1], b); }
+            }
+            ecl = {0.f, 0.f}; elj = {0.f, 0.f};
+        };
+        for (int t = tBegin; t < tEnd; t++) {
+            const int2 head = *reinterpret_cast<const int2*>(&p.tileInfo[t]);
+            const int slice = __builtin_amdgcn_readfirstlane(head.x & 0xFFFF), maskIdx = __builtin_amdgcn_readfirstlane(head.y);
+            const bool need = __builtin_amdgcn_readfirstlane(p.sliceNeed[slice]) != 0;
+            if (slice != curSlice) { if (curNeeded) flushEnergy(); curSlice = slice; curNeeded = need; }
+            if (!need) continue;      // (uniform) slice not wanted: the whole tile is skipped
+            const int code = p.tileJ[t * 32 + stageJ];
+            float4 pj = make_float4(3e9f + 1e6f * c, -5e9f, 7e9f, 0.f);      // padding slot: parked far away
+            float2 sej = make_float2(0.f, 0.f);
+            if (code != -1) {
+                const int idx = code & SNB_JIDX_MASK;
+                const float4 x = p.posq[idx];
+                const float4 sh = s_shift[(code >> SNB_JSHIFT_BITS) & 127];
+                pj = make_float4(x.x + sh.x, x.y + sh.y, x.z + sh.z, x.w); sej = p.sigeps[idx];
+            }
+            unsigned maskA = 0u, maskB = 0u;
+            if (maskIdx >= 0) { maskA = p.masks[maskIdx * 32 + c] >> (8 * row); maskB = p.masks[maskIdx * 32 + 16 + c] >> (8 * row); }
+            const float lamL = p.lambdas[2 * slice + 1];
+            __builtin_amdgcn_wave_barrier();
+            myPos[lane] = pj; mySe[lane] = sej;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            v2f fix = {0.f, 0.f}, fiy = {0.f, 0.f}, fiz = {0.f, 0.f};      // (not touched: FORCES == false)
+            float fjx = 0.f, fjy = 0.f, fjz = 0.f;
+            if (maskIdx >= 0) tileStepsPacked<MC, true, POLY, true, SWITCH, false>(p, rdPos, rdSe, pix, piy, piz, sigi, qi, epsi, qi, epsi, c6i, lamL, maskA, maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj);
+            else tileStepsPacked<MC, false, POLY, true, SWITCH, false>(p, rdPos, rdSe, pix, piy, piz, sigi, qi, epsi, qi, epsi, c6i, lamL, maskA, maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj);
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (curNeeded) flushEnergy();
+    }
+}
+
 
 // evStart/evStop (both or neither): hipExtLaunchKernelGGL stamps them with the kernel's own begin and end -- the duration rocprofv3 reports,
 // without the marker-packet overhead of hipEventRecord pairs around the launch.  *timed tells the caller whether a kernel took them.
@@ -810,8 +973,46 @@ template <typename Real> bool launchDirect(const DirectParams<Real>& p0, int mc,
 template bool launchDirect<float>(const DirectParams<float>&, int, bool, bool, const PairListParams<float>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
 template bool launchDirect<double>(const DirectParams<double>&, int, bool, bool, const PairListParams<double>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
 
+// Energy-only step (include_forces == 0): k_directPackedEnergy wherever the forces step runs k_directPacked, k_directEnergy elsewhere (double
+// precision, per-pair wrapping; the guard on a NoCutoff switch only mirrors launchDirectMC -- the engine never sets useSwitch for NoCutoff).
+// The pair lists passed in `lists` always ride along; returns whether there were any.
+template <typename Real, int MC> static bool launchDirectEnergyMC(const DirectParams<Real>& p, bool wrap, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
+    if (p.numWork <= 0) return false;
+    dim3 block(256);
+    PairListParams<Real> q;
+    std::memset(&q, 0, sizeof(q));
+    int nExclBlocks = 0, nListBlocks = 0;
+    if (lists) { q = *lists; nExclBlocks = (q.nExclAtoms + 255) / 256; nListBlocks = nExclBlocks + (q.n + 255) / 256; }
+    const size_t listLds = lists ? sizeof(double) * 2 * q.nSlices : 0;
+    const dim3 gridAll((p.numWork + 3) / 4 + nListBlocks);
+    if constexpr (std::is_same<Real, float>::value) {
+        if (!wrap && !(p.useSwitch && MC == MC_NOCUTOFF)) {
+            const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && p.ewUsePoly;
+#define SNB_PACKED_E(P, S) SNB_LAUNCH_LDS((k_directPackedEnergy<MC, P, S>), gridAll, listLds, p, q, nExclBlocks, nListBlocks)
+            if constexpr (MC == MC_NOCUTOFF) SNB_PACKED_E(false, false);
+            else if (p.useSwitch && MC != MC_LJPME) { if (poly) SNB_PACKED_E(true, true); else SNB_PACKED_E(false, true); }
+            else { if (poly) SNB_PACKED_E(true, false); else SNB_PACKED_E(false, false); }
+#undef SNB_PACKED_E
+            return lists != nullptr;
+        }
+    }
+    if (wrap) SNB_LAUNCH_LDS((k_directEnergy<Real, MC, true>), gridAll, listLds, p, q, nExclBlocks, nListBlocks);
+    else SNB_LAUNCH_LDS((k_directEnergy<Real, MC, false>), gridAll, listLds, p, q, nExclBlocks, nListBlocks);
+    return lists != nullptr;
+}
+template <typename Real> bool launchDirectEnergy(const DirectParams<Real>& p, int mc, bool wrap, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
+    switch (mc) {
+        case MC_NOCUTOFF: return launchDirectEnergyMC<Real, MC_NOCUTOFF>(p, wrap, lists, s, evStart, evStop, timed);
+        case MC_RF: return launchDirectEnergyMC<Real, MC_RF>(p, wrap, lists, s, evStart, evStop, timed);
+        case MC_EWALD: return launchDirectEnergyMC<Real, MC_EWALD>(p, wrap, lists, s, evStart, evStop, timed);
+        default: return launchDirectEnergyMC<Real, MC_LJPME>(p, wrap, lists, s, evStart, evStop, timed);
+    }
+}
+template bool launchDirectEnergy<float>(const DirectParams<float>&, int, bool, const PairListParams<float>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
+template bool launchDirectEnergy<double>(const DirectParams<double>&, int, bool, const PairListParams<double>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
+
 // ---- 1-4 exceptions: ReferenceSlicedLJCoulomb14.cpp:61-95 ----------------------------------------
-template <typename Real, bool ENERGY> __device__ __forceinline__ void exceptionsBody(const PairListParams<Real>& p, const int blk) {
+template <typename Real, bool ENERGY, bool FORCES> __device__ __forceinline__ void exceptionsBody(const PairListParams<Real>& p, const int blk) {
     extern __shared__ double s_sliceE[];   // [2*S]
     const int nS2 = 2 * p.nSlices;
     if (ENERGY) { for (int i = threadIdx.x; i < nS2; i += 256) s_sliceE[i] = 0.0; __syncthreads(); }
@@ -832,8 +1033,10 @@ template <typename Real, bool ENERGY> __device__ __forceinline__ void exceptions
         const Real lamC = p.lambdas[2 * slice], lamL = p.lambdas[2 * slice + 1];
         Real dEdR = lamL * par.y * (Real(12) * s6 - Real(6)) * s6 + lamC * par.z * invR;
         dEdR *= invR * invR;
+        if constexpr (FORCES) {
         fAdd(p, p.fx, ij.x, dEdR * dx); fAdd(p, p.fy, ij.x, dEdR * dy); fAdd(p, p.fz, ij.x, dEdR * dz);
         fAdd(p, p.fx, ij.y, -dEdR * dx); fAdd(p, p.fy, ij.y, -dEdR * dy); fAdd(p, p.fz, ij.y, -dEdR * dz);
+        }
         if (ENERGY && p.sliceNeed[slice]) { e0 = par.z * invR; e1 = par.y * (s6 - Real(1)) * s6; }
     }
     if (ENERGY) {
@@ -851,7 +1054,7 @@ template <typename Real, bool ENERGY> __device__ __forceinline__ void exceptions
 // from both ends, so the force update is a plain read-modify-write of the atom's own accumulator -- no atomics
 // (2 M scattered float atomics cost 70 us on MI355X; this costs a few us).  Energies: half a pair from each end,
 // reduced per slice in LDS (ds_add_f64) and flushed with one global atomic per slice and work-group.
-template <typename Real, bool ENERGY> __device__ __forceinline__ void exclusionAtomsBody(const PairListParams<Real>& p, const int blk) {
+template <typename Real, bool ENERGY, bool FORCES> __device__ __forceinline__ void exclusionAtomsBody(const PairListParams<Real>& p, const int blk) {
     extern __shared__ double s_sliceE[];   // [2*S]
     const int nS2 = 2 * p.nSlices;
     if (ENERGY) { for (int i = threadIdx.x; i < nS2; i += 256) s_sliceE[i] = 0.0; __syncthreads(); }
@@ -888,6 +1091,7 @@ template <typename Real, bool ENERGY> __device__ __forceinline__ void exclusionA
                 // 2e5 identical pairs, which alone was 0.8 kJ/mol (1.1e-3 of the water-water slice of the 96k-atom box).
                 double erfv, rd = 0, qqd = 0;
                 const bool wantE = ENERGY && p.sliceNeed[slice] != 0;
+                if constexpr (!FORCES) { if (!wantE) continue; }
                 if (wantE) {
                     rd = sqrt((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
                     qqd = (double)xi.w * (double)xj.w * SNB_ONE_4PI_EPS0;
@@ -912,7 +1116,7 @@ template <typename Real, bool ENERGY> __device__ __forceinline__ void exclusionA
                 }
                 fx += f * dx; fy += f * dy; fz += f * dz;
             }
-            fAdd(p, p.fx, a, fx); fAdd(p, p.fy, a, fy); fAdd(p, p.fz, a, fz);   // atomics: the 1-4 blocks of the same launch add to the same atoms
+            if constexpr (FORCES) { fAdd(p, p.fx, a, fx); fAdd(p, p.fy, a, fy); fAdd(p, p.fz, a, fz); }   // atomics: the 1-4 blocks of the same launch add to the same atoms
         }
     }
     if (ENERGY) {
@@ -937,5 +1141,17 @@ template <typename Real> void launchPairLists(const PairListParams<Real>& p, boo
 }
 template void launchPairLists<float>(const PairListParams<float>&, bool, hipStream_t);
 template void launchPairLists<double>(const PairListParams<double>&, bool, hipStream_t);
+// the same two lists with energies alone (steps with include_forces == 0 whose tile kernel did not take them)
+template <typename Real> __global__ __launch_bounds__(256) void k_pairListsEnergy(const PairListParams<Real> p, const int nExclBlocks) {
+    if ((int)blockIdx.x < nExclBlocks) { PairListParams<Real> q = p; q.n = p.nExclAtoms; exclusionAtomsBody<Real, true, false>(q, blockIdx.x); }
+    else exceptionsBody<Real, true, false>(p, blockIdx.x - nExclBlocks);
+}
+template <typename Real> void launchPairListsEnergy(const PairListParams<Real>& p, hipStream_t s) {
+    const int nExclBlocks = (p.nExclAtoms + 255) / 256, nExcBlocks = (p.n + 255) / 256;
+    if (nExclBlocks + nExcBlocks <= 0) return;
+    hipLaunchKernelGGL((k_pairListsEnergy<Real>), dim3(nExclBlocks + nExcBlocks), dim3(256), sizeof(double) * 2 * p.nSlices, s, p, nExclBlocks);
+}
+template void launchPairListsEnergy<float>(const PairListParams<float>&, hipStream_t);
+template void launchPairListsEnergy<double>(const PairListParams<double>&, hipStream_t);
 
 }  // namespace snb

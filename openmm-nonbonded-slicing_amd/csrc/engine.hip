@@ -279,15 +279,39 @@ public:
     int forceArrays() const { return fixedForces() ? 10 : 7; }
     void layoutForces() {
         forceBuf.resize((size_t)forceArrays() * Npad);
-        if (fixedForces()) {
-            fstride = 1;
-            fx.p = forceBuf.p; fy.p = fx.p + 2 * (size_t)Npad; fz.p = fx.p + 4 * (size_t)Npad;      // bases of 64-bit arrays
-            fpx.p = forceBuf.p + 7 * (size_t)Npad; fpy.p = fpx.p + Npad; fpz.p = fpy.p + Npad;
-            return;
-        }
+        pointForceViews(forceBuf.p);
+    }
+    // the views over a force set: forceBuf, or (energy-only steps of sharded PME engines, whose energies come from the force interpolation)
+    // forceScratch, so that such a step leaves the engine's forces alone
+    Real* forceBase = nullptr;
+    DevBuf<Real> forceScratch;
+    struct ForceSet { Real *x, *y, *z, *px, *py, *pz; };
+    ForceSet forceSet(Real* base, int npad) const {      // component bases of a force set laid out for npad padded atoms
+        if (fixedForces())      // (three arrays of 64-bit words, then the three reciprocal arrays)
+            return {base, base + 2 * (size_t)npad, base + 4 * (size_t)npad, base + 7 * (size_t)npad, base + 8 * (size_t)npad, base + 9 * (size_t)npad};
+        return {base, base + (size_t)npad, base + 2 * (size_t)npad, base + 4 * (size_t)npad, base + 5 * (size_t)npad, base + 6 * (size_t)npad};
+    }
+    void pointForceViews(Real* base) {
+        forceBase = base;
         fstride = 1;
-        fx.p = forceBuf.p; fy.p = fx.p + Npad; fz.p = fx.p + 2 * (size_t)Npad;
-        fpx.p = forceBuf.p + 4 * (size_t)Npad; fpy.p = fpx.p + Npad; fpz.p = fpy.p + Npad;
+        const ForceSet v = forceSet(base, Npad);
+        fx.p = v.x; fy.p = v.y; fz.p = v.z; fpx.p = v.px; fpy.p = v.py; fpz.p = v.pz;
+    }
+    // The forces of the last forces step across the rebuilds of energy-only steps.  The force arrays are in SORTED order: a rebuild re-sorts the
+    // atoms (new permutation, possibly a new padded count and a reallocated forceBuf) and a side-build exchange swaps the permutations, so
+    // before an energy-only step rebuilds, the force set and the user-to-sorted map it was accumulated under are copied aside (stream-ordered)
+    // and snb_get_forces reads that copy until the next forces step.
+    bool haveForceStep = false, keptValid = false, keptRecip = false;
+    int keptNpad = 0;
+    DevBuf<Real> keptForces;
+    DevBuf<int> keptUserToSorted;
+    void keepLastForces() {
+        if (!haveForceStep || keptValid) return;
+        const size_t n = (size_t)forceArrays() * Npad;
+        keptForces.resize(n); keptUserToSorted.resize(std::max(N, 1));
+        HIPCHECK(hipMemcpyAsync(keptForces.p, forceBuf.p, sizeof(Real) * n, hipMemcpyDeviceToDevice, stream));
+        if (N > 0) HIPCHECK(hipMemcpyAsync(keptUserToSorted.p, dUserToSorted.p, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
+        keptNpad = Npad; keptRecip = lastRecip; keptValid = true;
     }
     DevBuf<int> pmeCells, dZIndex, dScanA, dScanB, dScanC, dAtomCell, dExtent;
     double tileCell[9] = {0};      // the cell the tile image codes refer to (the box; an enclosing cell for CutoffNonPeriodic)
@@ -1441,8 +1465,10 @@ public:
     }
 
     void execute(int includeForces, int includeEnergy, int includeDirect, int includeRecip, double* energyOut) override {
-        (void)includeForces;
         if (includeEnergy == 2 && energyOut) { err = "snb_execute: include_energy == 2 (derivative-only step) delivers no total energy; pass energy = NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const bool forces = includeForces != 0;
+        if (!forces && includeEnergy == 0) { if (energyOut) *energyOut = 0.0; return; }      // nothing asked for: nothing enqueued
+        if (forces) keptValid = false;      // (this step's forces replace the kept ones)
         if (!haveParticles) throw HipError{"snb_execute: particles were not set"};
         if (!havePositions) throw HipError{"snb_execute: positions were not set"};
         if (isPeriodic()) {
@@ -1470,6 +1496,7 @@ public:
         if (flagsResetPending && hipEventQuery(evFlagsReset) == hipSuccess) flagsResetPending = false;
         const bool due = autoMode ? ((hDispFlags[0] != 0 && !flagsResetPending) || stepsSinceRebuild >= -cfg.rebuild_interval) : (cfg.rebuild_interval <= 1 || stepsSinceRebuild >= cfg.rebuild_interval);
         bool rebuilding = needRebuild || paramsDirty || due || cfg.neighbor_padding <= 0;
+        if (!forces && rebuilding) keepLastForces();      // (an in-line rebuild re-sorts the atoms, a side-build exchange swaps the permutations)
         if (sidePending) {
             // anything but the positions changed since the side build started: its list is of no use
             if (needRebuild || paramsDirty || staticDirty || valuesDirty || excValuesDirty || cfg.neighbor_padding <= 0) cancelSideBuild();
@@ -1478,10 +1505,10 @@ public:
         if ((valuesDirty || excValuesDirty) && !staticDirty && !rebuilding) refreshValues();
         if (rebuilding) { if (valuesDirty || excValuesDirty) { staticDirty = true; valuesDirty = excValuesDirty = false; } rebuild(); }
         stepsSinceRebuild++;
-        outputWritten = outPtr != nullptr;
+        if (forces) outputWritten = outPtr != nullptr;      // (an energy-only step leaves the forces of the last forces step where they are)
         const bool energy = includeEnergy != 0;
         energySelective = includeEnergy == 2;      // derivative-only step: only the slices named by snb_set_energy_slices
-        lastRecip = includeRecip && (isPme() || cfg.method == SNB_Ewald);
+        if (forces) lastRecip = includeRecip && (isPme() || cfg.method == SNB_Ewald);
         // Forces-only steps replay a captured hipGraph (the ~14 small launches of a step are host-launch-bound otherwise:
         // 7-8 us of idle GPU between kernels).  Every 32nd step -- and every energy step -- is enqueued eagerly with HIP events
         // around the pair kernel and the reciprocal pipeline; those samples feed snb_stats' kernel timers.
@@ -1493,6 +1520,24 @@ public:
         // they end with the device-side sum of the slice-energy partitions and leave the result there until it is asked for.
         // (round 4: a rebuild step replays its graph too when one exists for these buffers -- refreshing it costs the host ~20 us of capture +
         // hipGraphExecUpdate, against ~40 us of launch gaps of an eager step, and an overlapped step is 37 us shorter than a serial one)
+        if (!forces) {
+            // Energy-only step (include_forces == 0): plain launches, timed on the eager steps' cadence; the step itself never captures or
+            // updates a step graph (a rebuild it performs marks the graphs stale, as any rebuild does).  No force arithmetic, no force stores,
+            // no force output -- except on sharded PME engines, whose energies come from the force interpolation: they run the forces kernels
+            // into a scratch set.
+            EvSet* ev = nullptr;
+            if (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0) {
+                ev = &ring[ringPos]; ringPos = (ringPos + 1) % RING;
+                if (ev->pending) harvest(*ev);
+            }
+            const bool scratch = includeRecip && isPme() && nGrids > 0 && cfg.shard_count > 1;
+            if (scratch) { forceScratch.resize((size_t)forceArrays() * Npad); pointForceViews(forceScratch.p); }
+            try { enqueueStep(energy, includeDirect != 0, includeRecip != 0, ev, scratch ? StepForces::Scratch : StepForces::None); }
+            catch (...) { if (scratch) pointForceViews(forceBuf.p); throw; }
+            if (scratch) pointForceViews(forceBuf.p);
+            if (ev) ev->pending = true;
+        } else {
+        haveForceStep = true;
         const GraphKey stepKey{devUserPos, posIsDouble, posStride4, includeDirect != 0, includeRecip != 0, energy ? (energySelective ? 2 : 1) : 0, outPtr, outIsDouble, outAccumulate};
         bool haveGraph = false;
         for (auto& g : graphs) if (g.key == stepKey && g.exec) haveGraph = true;
@@ -1551,6 +1596,7 @@ public:
               } else HIPCHECK(hipGraphLaunch(graphExec, stream)); }
             if (overlapMode && dOverlap.p) { static int dbg = getenv("SNB_OVERLAP_DEBUG") ? 3 : 0; if (dbg > 0) { dbg--; dumpOverlapTable(); } }
         }
+        }      // forces step
         if (autoMode && cfg.neighbor_padding > 0) {
             hipEvent_t& ev = evStepDone[stepCounter & 1];
             if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -1601,8 +1647,15 @@ public:
         energyPending = false;
     }
 
-    void enqueueStep(bool energy, bool includeDirect, bool includeRecip, EvSet* ev) {
+    // What a step does with forces: Full -- a forces step (accumulate, deliver to the force output); None -- an energy-only step (the
+    // energy-only kernels: no force arithmetic, nothing cleared, nothing stored); Scratch -- the forces kernels into whatever set the views
+    // point at, no delivery (energy-only steps of sharded PME engines).
+    enum class StepForces { Full, None, Scratch };
+    void enqueueStep(bool energy, bool includeDirect, bool includeRecip, EvSet* ev, StepForces fmode = StepForces::Full) {
         struct StampScope { StampScope(KernelStamps* k) { g_stamps = k; } ~StampScope() { g_stamps = nullptr; } };
+        const bool forces = fmode != StepForces::None;
+        const bool graphStep = !ev && fmode == StepForces::Full;      // (replayed forces steps: the only ones that overlap, fork or trace)
+        void* const out = fmode == StepForces::Full ? outPtr : nullptr;
         if (ev) for (int k = 0; k < 16; k++) ev->ks.used[k] = false;
         static const bool noStamps = getenv("SNB_NO_KERNEL_STAMPS") != nullptr;      // measurement aid: only the pair-kernel / pipeline timers
         // (a stamped launch completes a signal of its own: ~8 us per kernel, 70 us per step with every PME kernel stamped -- measured: 20-step
@@ -1632,17 +1685,17 @@ public:
         }
         if (energy && Npad > 0) { gc.clearE = sliceE.p; gc.nClearE = S * 2 * SNB_SLICE_E_PARTS; }
         if (includeRecip && isPme() && dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
-        if (!ev && overlapMode && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
-        traceThisStep = !ev && dStepTrace.p != nullptr;      // (SNB_STEP_TRACE; replayed steps only: the stamps of the last one are printed when the engine is destroyed)
+        if (graphStep && overlapMode && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
+        traceThisStep = graphStep && dStepTrace.p != nullptr;      // (SNB_STEP_TRACE; replayed steps only: the stamps of the last one are printed when the engine is destroyed)
         gc.stepTrace = traceThisStep ? dStepTrace.p : nullptr;
-        launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBuf.p, forceArrays(), gc, stream);
+        launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream);
         if (energy && Npad <= 0) launchZeroFill(sliceE.p, sizeof(double) * S * 2 * SNB_SLICE_E_PARTS, stream);      // (inside the step graph: a kernel, not a memset node)
         const bool ew = cfg.method >= SNB_Ewald;
         // Opt-in (SNB_CONCURRENT_PME=1): forces-only graph steps run the reciprocal pipeline on a second stream beside the pair
         // kernel (disjoint force arrays fx.. / fpx..).  Timed (eager) steps stay serial so the per-kernel event timers stay clean.
         // overlapped step (see overlapMode above): any graph step with both halves; needs the GPU-built work list (static item order is irrelevant)
-        const bool overlap = !ev && overlapMode && includeDirect && includeRecip && isPme() && nGrids > 0 && stream2 && dOverlap.p && numWorkItems > 0 && shardTiles >= overlapMinTiles;
-        const bool fork = overlap || (!ev && !energy && includeDirect && includeRecip && isPme() && nGrids > 0 && concurrentPme && stream2);
+        const bool overlap = graphStep && overlapMode && includeDirect && includeRecip && isPme() && nGrids > 0 && stream2 && dOverlap.p && numWorkItems > 0 && shardTiles >= overlapMinTiles;
+        const bool fork = overlap || (graphStep && !energy && includeDirect && includeRecip && isPme() && nGrids > 0 && concurrentPme && stream2);
         hipStream_t pmeStream = stream;
         if (fork) {
             HIPCHECK(hipEventRecord(evFork, stream));
@@ -1707,10 +1760,11 @@ public:
                 p.cuTrace = dOverlapTrace.p;      // (SNB_OVERLAP_DEBUG; null otherwise)
                 directB = p; directMc = mc;
             }
-            if (launchDirect<Real>(p, mc, wrapMode, energy, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true;
+            if (!forces) { if (launchDirectEnergy<Real>(p, mc, wrapMode, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true; }
+            else if (launchDirect<Real>(p, mc, wrapMode, energy, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true;
         }
         if (ev && !kernelTimed) { HIPCHECK(hipEventRecord(ev->e[1], stream)); HIPCHECK(hipEventRecord(ev->e[2], stream)); }   // no tile kernel this step
-        if (!listsDone) launchPairLists<Real>(q, energy, stream);
+        if (!listsDone) { if (forces) launchPairLists<Real>(q, energy, stream); else launchPairListsEnergy<Real>(q, stream); }
         if (overlap) HIPCHECK(hipEventRecord(evPairA, stream));      // the first launch of the tile kernel (and the pair lists) are done
         if (ev) HIPCHECK(hipEventRecord(ev->e[3], stream));
         if (includeRecip && isPme()) {
@@ -1721,10 +1775,10 @@ public:
                 // reciprocal work on the step's own stream (the pair kernel's accumulators are complete by then)
                 static const bool noFuse = getenv("SNB_NO_FUSED_FINISH") != nullptr;
                 // (an overlapped step keeps the fused finish: its last interpolation waits for both launches of the tile kernel)
-                const bool canFinish = outPtr && (!fork || overlap) && !noFuse && cfg.shard_count == 1;
+                const bool canFinish = out && (!fork || overlap) && !noFuse && cfg.shard_count == 1;
                 static const bool noFusedE = getenv("SNB_NO_FUSED_ENERGY_FINISH") != nullptr;      // test switch: k_finishSliceEnergies as a kernel of its own
                 auto withOutput = [&](PmeParams<Real>& q, bool last) {
-                    q.outForces = (canFinish && last) ? outPtr : nullptr; q.outIsDouble = outIsDouble; q.outAccumulate = outAccumulate;
+                    q.outForces = (canFinish && last) ? out : nullptr; q.outIsDouble = outIsDouble; q.outAccumulate = outAccumulate;
                     q.finOut = nullptr;
                     if (canFinish && last && energy && q.mix && !noFusedE) { q.finParts = sliceE.p; q.finOut = sliceTotal.p; q.finN = 2 * S; q.fin = makeSliceFinish(includeDirect, includeRecip); }
                     q.dfx = fx.p; q.dfy = fy.p; q.dfz = fz.p; q.dfs = fstride; q.dfixed = fixedForces(); q.sortedToUser = dSortedToUser.p;
@@ -1739,25 +1793,24 @@ public:
                     launchDirect<Real>(directB, directMc, wrapMode, energy, nullptr, stream2, nullptr, nullptr, &t);
                     HIPCHECK(hipStreamWaitEvent(stream2, evPairA, 0));
                 };
-                fillPme(pp, pme, energy); withOutput(pp, cfg.method != SNB_LJPME);
+                // (energy-only steps: each mesh ends with its slice-energy Gram sums -- no mix, no inverse transforms, no interpolation)
+                fillPme(pp, pme, energy); withOutput(pp, cfg.method != SNB_LJPME); pp.energyOnly = forces ? 0 : 1;
                 runPmeFront(pp, pmeStream);
                 if (cfg.method != SNB_LJPME) beforeLastInterpolation();
-                finished = launchPmeInterpolate<Real>(pp, pmeStream);
-                energyFinished = finished && pp.finOut != nullptr;
+                if (forces) { finished = launchPmeInterpolate<Real>(pp, pmeStream); energyFinished = finished && pp.finOut != nullptr; }
                 if (cfg.method == SNB_LJPME) {
-                    fillPme(pp, dpme, energy); withOutput(pp, true);
+                    fillPme(pp, dpme, energy); withOutput(pp, true); pp.energyOnly = forces ? 0 : 1;
                     runPmeFront(pp, pmeStream);
                     beforeLastInterpolation();
-                    finished = launchPmeInterpolate<Real>(pp, pmeStream);
-                    energyFinished = finished && pp.finOut != nullptr;
+                    if (forces) { finished = launchPmeInterpolate<Real>(pp, pmeStream); energyFinished = finished && pp.finOut != nullptr; }
                 }
             }
         }
         if (fork) { HIPCHECK(hipEventRecord(evJoin, stream2)); HIPCHECK(hipStreamWaitEvent(stream, evJoin, 0)); }
-        if (includeRecip && cfg.method == SNB_Ewald && cfg.shard_rank == 0) runEwald(energy);
-        if (outPtr && !finished) {   // the step's last kernel: user-order forces into the caller's buffer (part of the graph)
+        if (includeRecip && cfg.method == SNB_Ewald && cfg.shard_rank == 0) runEwald(energy, forces);
+        if (out && !finished) {   // the step's last kernel: user-order forces into the caller's buffer (part of the graph)
             const bool recipDone = includeRecip && (isPme() || cfg.method == SNB_Ewald);
-            launchFinishForces<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), recipDone ? fpx.p : nullptr, fpy.p, fpz.p, dUserToSorted.p, N, outPtr, outIsDouble, outAccumulate, stream);
+            launchFinishForces<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), recipDone ? fpx.p : nullptr, fpy.p, fpz.p, dUserToSorted.p, N, out, outIsDouble, outAccumulate, stream);
         }
         if (energy) {
             const SliceFinish f = makeSliceFinish(includeDirect, includeRecip);
@@ -1785,7 +1838,7 @@ public:
     }
 
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
-    void runEwald(bool energy) {
+    void runEwald(bool energy, bool forces) {
         if (hKvec.empty()) {
             int lowry = 0, lowrz = 1;
             for (int rx = 0; rx < cfg.kmax[0]; rx++) {
@@ -1803,7 +1856,7 @@ public:
         q.recipBox[0] = (Real)(2 * SNB_PI / box[0]); q.recipBox[1] = (Real)(2 * SNB_PI / box[4]); q.recipBox[2] = (Real)(2 * SNB_PI / box[8]);
         q.factorEwald = -1 / (4 * cfg.alpha * cfg.alpha); q.recipCoeff = SNB_ONE_4PI_EPS0 * 4 * SNB_PI / (box[0] * box[4] * box[8]);
         q.lambdas = dLambdas.p; q.sliceE = sliceE.p; q.wantEnergy = energy ? 1 : 0; q.fpx = fpx.p; q.fpy = fpy.p; q.fpz = fpz.p;
-        launchEwald<Real>(q, stream);
+        launchEwald<Real>(q, stream, forces);      // (forces == false: structure factors and energies only)
     }
 
     void harvest(EvSet& ev) {
@@ -1830,7 +1883,7 @@ public:
         else {
             launchPmeForwardFFT<Real>(pp, st, zDone == 1);
             launchPmeConvolution<Real>(pp, st);
-            launchPmeInverseFFT<Real>(pp, st);
+            if (!pp.energyOnly) launchPmeInverseFFT<Real>(pp, st);
         }
     }
 
@@ -1838,11 +1891,14 @@ public:
     void getForces(void* out, int isDevice, int isDouble, int accumulate) override {
         if (isDevice && out == outPtr && isDouble == outIsDouble && outputWritten) return;   // the last execute already delivered them there
         const size_t bytes = (size_t)N * 3 * (isDouble ? 8 : 4);
-        const Real* px = lastRecip ? fpx.p : nullptr;
-        if (isDevice) { launchFinishForces<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), px, fpy.p, fpz.p, dUserToSorted.p, N, out, isDouble, accumulate, stream); return; }
+        // the live force set, or the copy kept before an energy-only step re-sorted the atoms (keepLastForces)
+        const ForceSet f = keptValid ? forceSet(keptForces.p, keptNpad) : ForceSet{fx.p, fy.p, fz.p, fpx.p, fpy.p, fpz.p};
+        const int* u2s = keptValid ? keptUserToSorted.p : dUserToSorted.p;
+        const Real* px = (keptValid ? keptRecip : lastRecip) ? f.px : nullptr;
+        if (isDevice) { launchFinishForces<Real>(f.x, f.y, f.z, fstride, fixedForces(), px, f.py, f.pz, u2s, N, out, isDouble, accumulate, stream); return; }
         DevBuf<unsigned char> tmp; tmp.resize(bytes);
         if (accumulate) HIPCHECK(hipMemcpyAsync(tmp.p, out, bytes, hipMemcpyHostToDevice, stream));
-        launchFinishForces<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), px, fpy.p, fpz.p, dUserToSorted.p, N, tmp.p, isDouble, accumulate, stream);
+        launchFinishForces<Real>(f.x, f.y, f.z, fstride, fixedForces(), px, f.py, f.pz, u2s, N, tmp.p, isDouble, accumulate, stream);
         HIPCHECK(hipMemcpyAsync(out, tmp.p, bytes, hipMemcpyDeviceToHost, stream));
         HIPCHECK(hipStreamSynchronize(stream));
     }

@@ -79,12 +79,13 @@ template <typename Real> __global__ __launch_bounds__(256) void k_ewaldForces(co
     p.fpx[a] = (Real)fx; p.fpy[a] = (Real)fy; p.fpz[a] = (Real)fz;
 }
 
-template <typename Real> void launchEwald(const EwaldParams<Real>& p, hipStream_t s) {
+// forces == false (steps with include_forces == 0): the structure factors and the slice energies (k_ewaldSums), no force pass
+template <typename Real> void launchEwald(const EwaldParams<Real>& p, hipStream_t s, bool forces) {
     if (p.nk <= 0 || p.natoms <= 0) return;
     hipLaunchKernelGGL((k_ewaldSums<Real>), dim3(p.nk), dim3(256), sizeof(double) * 2 * p.nsub, s, p);
-    hipLaunchKernelGGL((k_ewaldForces<Real>), dim3((p.natoms + 255) / 256), dim3(256), 0, s, p);
+    if (forces) hipLaunchKernelGGL((k_ewaldForces<Real>), dim3((p.natoms + 255) / 256), dim3(256), 0, s, p);
 }
-template void launchEwald<float>(const EwaldParams<float>&, hipStream_t);
-template void launchEwald<double>(const EwaldParams<double>&, hipStream_t);
+template void launchEwald<float>(const EwaldParams<float>&, hipStream_t, bool);
+template void launchEwald<double>(const EwaldParams<double>&, hipStream_t, bool);
 
 }  // namespace snb

@@ -1162,7 +1162,8 @@ template <typename Real> __device__ inline Real recipTerm(const PmeParams<Real>&
 // One work-group owns NB adjacent (ky,kz) columns for ALL held subsets: batch index = sub*NB + col.
 // (NT = 256 for double precision with a 15- or 16-point register transform: at 512 threads the kernel is capped at 128 VGPRs and spilled
 // -- 351 -> 488 us on c5's 180^3 mesh in round 3, which therefore stayed on the staged transform; at 256 threads it has 256)
-template <typename Real, int R1, int R2, int NT = 512> __global__ __launch_bounds__(NT) void k_convolveX(const PmeParams<Real> p, int NB, int nCols) {
+// EONLY (steps with include_forces == 0): the x transform and the slice-energy Gram sums, then nothing -- no mix, no inverse x, no store
+template <typename Real, int R1, int R2, int NT = 512, bool EONLY = false> __global__ __launch_bounds__(NT) void k_convolveX(const PmeParams<Real> p, int NB, int nCols) {
     const int nx = p.d.nx, nsub = p.nsub;
     const int BS = nsub * NB;
     const int c0 = blockIdx.x * NB;
@@ -1251,6 +1252,7 @@ template <typename Real, int R1, int R2, int NT = 512> __global__ __launch_bound
             }
         if (ng > 0) flushGroup();
     }
+    if constexpr (EONLY) return;
     // convolution with the lambda mix:  O_I = eterm * sum_J lambda[slice(I,J)][term] * S_J   (mix=0: O_I = eterm * S_I)
     bool mixedOnMatrixCores = false;
     if constexpr (std::is_same<Real, float>::value) {
@@ -1470,7 +1472,10 @@ template <typename Real> __global__ __launch_bounds__(256) void k_planeEterm(con
     table[i] = recipTerm<Real>(p, px / p.d.px2 + p.d.px1 * (px % p.d.px2), py / p.d.py2 + p.d.py1 * (py % p.d.py2), kz);      // (each axis in the permuted order of its own in-place transform)
 }
 
-template <int R1, int R2, int NT> __global__ __launch_bounds__(NT) void k_planeXY(const PmeParams<float> p, const int NBY) {
+// EONLY (steps with include_forces == 0): the slice energies alone -- the convolved plane is not stored and k_fftZInvMix does not follow.
+// (The inverse x / y passes stay: the Gram sums are taken by Parseval against the real-space plane Q~_I of the other work-groups' slots,
+// which this work-group has only in (x, y, kz) space.)
+template <int R1, int R2, int NT, bool EONLY = false> __global__ __launch_bounds__(NT) void k_planeXY(const PmeParams<float> p, const int NBY) {
     SNB_PME_PRIO();
     SNB_TRACE_START(p.stepTrace, 8);
     using Real = float;
@@ -1549,6 +1554,7 @@ template <int R1, int R2, int NT> __global__ __launch_bounds__(NT) void k_planeX
         planePassDyn<+1, 2, true>(sp.ry1(), 0, nx, PY, 1, sp.ry2(), twYOff, tid, NT, PlaneNoScale());
         __syncthreads();
     }
+    if constexpr (!EONLY)
     batchedCopy<8, float4>(tid, nPairs, NT,
         [&](int e) { const int x = dny.div(2 * e), y = 2 * e - x * ny; const Cx<Real> a = P[x * PY + y], b = P[x * PY + y + 1]; return make_float4(a.x, a.y, b.x, b.y); },
         [&](int e, const float4& v) { const int x = dny.div(2 * e), y = 2 * e - x * ny, t = dNBY.div(y); *reinterpret_cast<float4*>(out + ((size_t)x * tilesY + t) * tileStride + (y - t * NBY)) = v; });
@@ -1731,6 +1737,19 @@ template <typename Real> static void launchFftStrided(int r1, int r2, dim3 grid,
     SNB_STAMPED_LAUNCH(axis == 1 ? stampSlot(p, sign < 0 ? 3 : 5) : -1, (k_fftStrided<Real, 0, 0>), grid, dim3(fftyThreads()), lds, s, p, n, strideA, nbTotal, strideK, NB, tilesPerA, sign, axis);
 }
 template <typename Real> static void launchConvolveX(int r1, int r2, dim3 grid, size_t lds, hipStream_t s, const PmeParams<Real>& p, int NB, int nCols) {
+    if (p.energyOnly) {      // energy-only steps: the same split and thread count as the forces step's kernel, so the Gram sums are the same
+#define X(A, B) if (r1 == A && r2 == B) { \
+        if constexpr (sizeof(Real) == 8 && (A > 12 || B > 12)) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+                                                                 SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B, 256, true>), grid, dim3(256), lds, s, p, NB, nCols); } \
+        else { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+               SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B, 512, true>), grid, dim3(512), lds, s, p, NB, nCols); } \
+        return; }
+        SNB_FFT_PAIRS(X)
+#undef X
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, 0, 0, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, 0, 0, 512, true>), grid, dim3(512), lds, s, p, NB, nCols);
+        return;
+    }
 #define X(A, B) if (r1 == A && r2 == B) { \
         if constexpr (sizeof(Real) == 8 && (A > 12 || B > 12)) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                                                                  SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B, 256>), grid, dim3(256), lds, s, p, NB, nCols); } \
@@ -1774,6 +1793,15 @@ static void launchPlaneXY(const PmeParams<float>& p, hipStream_t s) {
     const size_t lds = planeLds(p);
     const int NBY = planeTileY(p);
     const dim3 grid((unsigned)(p.nsub * p.d.nzc));
+    if (p.energyOnly) {      // energy-only steps: 1024 threads, the static split of a square plane or the run-time one
+#define X(A, B) if (planeSquare(p.d) && p.d.px1 == A && p.d.px2 == B) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<A, B, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+                                                                    SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<A, B, 1024, true>), grid, dim3(1024), lds, s, p, NBY); return; }
+        SNB_PLANE_PAIRS(X)
+#undef X
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<0, 0, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<0, 0, 1024, true>), grid, dim3(1024), lds, s, p, NBY);
+        return;
+    }
     static const int nt = getenv("SNB_PLANE_NT") ? atoi(getenv("SNB_PLANE_NT")) : 1024;      // threads per plane: 1024 or 768
     if (!planeSquare(p.d)) {      // rectangular plane: the kernel with run-time splits
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<0, 0, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1825,7 +1853,7 @@ template bool launchPlaneEterm<double>(const PmeParams<double>&, double*, hipStr
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s) {
     if constexpr (std::is_same<Real, float>::value) {
         launchPlaneXY(p, s);
-        launchFftZInvMix(p, s);
+        if (!p.energyOnly) launchFftZInvMix(p, s);      // (energy-only steps end with the plane kernel's Gram sums)
     }
 }
 template void launchPmePlanePath<float>(const PmeParams<float>&, hipStream_t);

@@ -210,6 +210,7 @@ template <typename Real> struct PmeParams {
     const double* finParts; double* finOut; int finN; SliceFinish fin;      // finOut != null: one work-group of the interpolation also sums the slice-energy partitions (the fused k_finishSliceEnergies)
     const Real* dfx; const Real* dfy; const Real* dfz; int dfs, dfixed;   // direct-space accumulators (component bases, atom stride, 64-bit fixed point)
     const int* sortedToUser;
+    int energyOnly;            // include_forces == 0 step: the chain ends with the slice-energy Gram sums (launchPmePlanePath / launchPmeConvolution)
 };
 
 // classic Ewald reciprocal sum (ewald.hip)
@@ -223,7 +224,7 @@ template <typename Real> struct EwaldParams {
     const Real* lambdas; double* sliceE; int wantEnergy;
     Real* fpx; Real* fpy; Real* fpz;
 };
-template <typename Real> void launchEwald(const EwaldParams<Real>& p, hipStream_t s);
+template <typename Real> void launchEwald(const EwaldParams<Real>& p, hipStream_t s, bool forces = true);   // forces == false: structure factors + slice energies only
 
 // GPU neighbour build (neighbor.hip)
 template <typename Real> struct NbParams {
@@ -271,6 +272,10 @@ void launchNeighborPublish(const int* counters, int* hostMapped, int seq, hipStr
 template <typename Real> bool launchDirect(const DirectParams<Real>& p, int methodClass, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s,
                                           hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr, bool* timed = nullptr);   // true: lists ran inside the launch
 template <typename Real> void launchPairLists(const PairListParams<Real>& p, bool energy, hipStream_t s);
+// include_forces == 0 steps: the slice energies of the tile kernel's tiles / of the two pair lists, no force arithmetic, no force stores
+template <typename Real> bool launchDirectEnergy(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, hipStream_t s,
+                                                 hipEvent_t evStart, hipEvent_t evStop, bool* timed);
+template <typename Real> void launchPairListsEnergy(const PairListParams<Real>& p, hipStream_t s);
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s);   // 1: forward z FFT already done; 2: ... and the spectrum is plane-major (plane path)
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s);   // rebuild time: fills the plane path's kernel-value table
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s);   // after a spreader that returned 2: k_planeXY + k_fftZInvMix instead of forward FFT, convolution, inverse FFT
