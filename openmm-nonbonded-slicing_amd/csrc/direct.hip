@@ -14,9 +14,9 @@
 // lambda scaling costs two multiplies per TILE and per-slice energies are two accumulators per tile -- there is no
 // per-pair slice arithmetic at all (the reference computes the slice index and loads LAMBDA[slice] per pair).
 #include "snb_internal.h"
+#include "switches.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
-#include <map>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -893,41 +893,17 @@ __global__ __launch_bounds__(256, 4) void k_directPackedEnergy(const DirectParam
 
 // evStart/evStop (both or neither): hipExtLaunchKernelGGL stamps them with the kernel's own begin and end -- the duration rocprofv3 reports,
 // without the marker-packet overhead of hipEventRecord pairs around the launch.  *timed tells the caller whether a kernel took them.
-// (a CU-limited launch of an overlapped step is told where its resident work-groups may sit: below (cuLimit - 1) allocations of this kernel)
-#define SNB_LAUNCH_LDS(KERNEL, GRID, LDS, P, ...) do { auto p_ = (P); if (p_.cuSlots && p_.cuLimit > 0 && p_.cuBaseMax == 0x7fffffff) p_.cuBaseMax = (p_.cuLimit - 1) * vgprUnits((const void*)(KERNEL)); \
-                                                    if (evStart) { hipExtLaunchKernelGGL(KERNEL, GRID, block, LDS, s, evStart, evStop, 0, p_, __VA_ARGS__); *timed = true; } \
-                                                    else hipLaunchKernelGGL(KERNEL, GRID, block, LDS, s, p_, __VA_ARGS__); } while (0)
-// register allocation of a kernel in the hardware's units of 8 VGPRs (accumulation registers included), looked up once per kernel
-static int vgprUnits(const void* kernel) {
-    static std::map<const void*, int> cache;
-    auto it = cache.find(kernel);
-    if (it != cache.end()) return it->second;
-    hipFuncAttributes attr;
-    int units = 16;
-    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess && attr.numRegs > 0) units = (attr.numRegs + 7) / 8;
-    cache[kernel] = units;
-    return units;
-}
-#define SNB_LAUNCH(KERNEL, GRID, ...) SNB_LAUNCH_LDS(KERNEL, GRID, 0, __VA_ARGS__)
-template <typename Real, int MC> static bool launchDirectMC(const DirectParams<Real>& p, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
-    const int myItems = p.numWork;
-    if (myItems <= 0) return false;
-    int nwg = (myItems + 3) / 4;
-    { static const int cap = getenv("SNB_DIRECT_WGS") ? atoi(getenv("SNB_DIRECT_WGS")) : 0; if (cap > 0 && nwg > cap) nwg = cap; }
-    if (p.workCounter && p.gridCap > 0) nwg = p.cuLimit > 0 ? p.gridCap : std::min(nwg, p.gridCap);      // overlapped step: resident waves claim their items
-    dim3 grid(nwg), block(256);
+#define SNB_LAUNCH_LDS(KERNEL, GRID, LDS, ...) do { if (evStart) { hipExtLaunchKernelGGL(KERNEL, GRID, block, LDS, s, evStart, evStop, 0, __VA_ARGS__); *timed = true; } \
+                                                 else hipLaunchKernelGGL(KERNEL, GRID, block, LDS, s, __VA_ARGS__); } while (0)
+template <typename Real> using TileKernel = void (*)(DirectParams<Real>, PairListParams<Real>, int, int);
+// The tile kernel of a forces step.  *packed: the single-precision packed kernel, which carries the pair lists whatever SNB_NO_FUSED_LISTS says.
+template <typename Real, int MC> static TileKernel<Real> directKernel(const DirectParams<Real>& p, bool wrap, bool energy, bool* packed) {
+    *packed = false;
     if constexpr (std::is_same<Real, float>::value) {
-        static const bool scalarEnergy = getenv("SNB_SCALAR_ENERGY_KERNEL") != nullptr;
-        if (!wrap && !(energy && scalarEnergy) && !(p.useSwitch && MC == MC_NOCUTOFF)) {
-            PairListParams<float> q;
-            std::memset(&q, 0, sizeof(q));
-            int nExclBlocks = 0, nListBlocks = 0;
-            if (lists) { q = *lists; nExclBlocks = (q.nExclAtoms + 255) / 256; nListBlocks = nExclBlocks + (q.n + 255) / 256; }
-            const size_t listLds = (lists && energy) ? sizeof(double) * 2 * q.nSlices : 0;      // the energy list bodies reduce per slice in LDS
-            dim3 gridAll(nwg + nListBlocks);
+        if (!wrap && !(energy && switches().scalarEnergyKernel) && !(p.useSwitch && MC == MC_NOCUTOFF)) {
+            *packed = true;
             const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && p.ewUsePoly;
-#define SNB_PACKED(P, E, S) do { if (p.fixed) SNB_LAUNCH_LDS((k_directPacked<MC, P, E, S, true>), gridAll, listLds, p, q, nExclBlocks, nListBlocks); \
-                                 else SNB_LAUNCH_LDS((k_directPacked<MC, P, E, S, false>), gridAll, listLds, p, q, nExclBlocks, nListBlocks); } while (0)
+#define SNB_PACKED(P, E, S) return p.fixed ? k_directPacked<MC, P, E, S, true> : k_directPacked<MC, P, E, S, false>
             if constexpr (MC == MC_NOCUTOFF) { if (energy) SNB_PACKED(false, true, false); else SNB_PACKED(false, false, false); }
             else if (p.useSwitch && MC != MC_LJPME) {      // (no switching function under LJPME, Q2)
                 if (energy) { if (poly) SNB_PACKED(true, true, true); else SNB_PACKED(false, true, true); }
@@ -937,27 +913,46 @@ template <typename Real, int MC> static bool launchDirectMC(const DirectParams<R
                 else { if (poly) SNB_PACKED(true, false, false); else SNB_PACKED(false, false, false); }
             }
 #undef SNB_PACKED
-            return lists != nullptr;
         }
     }
-    // the scalar tile kernel (double precision, per-pair wrapping, the switches above) carries the pair lists the same way
+    // the scalar tile kernel: double precision, per-pair wrapping, the switches above
+    if (wrap) return energy ? k_direct<Real, MC, true, true> : k_direct<Real, MC, true, false>;
+    return energy ? k_direct<Real, MC, false, true> : k_direct<Real, MC, false, false>;
+}
+template <typename Real, int MC> static bool launchDirectMC(const DirectParams<Real>& p, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
+    const int myItems = p.numWork;
+    if (myItems <= 0) return false;
+    int nwg = (myItems + 3) / 4;
+    { const int cap = switches().directWgs; if (cap > 0 && nwg > cap) nwg = cap; }
+    if (p.workCounter && p.gridCap > 0) nwg = p.cuLimit > 0 ? p.gridCap : std::min(nwg, p.gridCap);      // overlapped step: resident waves claim their items
+    bool packed;
+    const TileKernel<Real> kernel = directKernel<Real, MC>(p, wrap, energy, &packed);
     PairListParams<Real> q;
     std::memset(&q, 0, sizeof(q));
     int nExclBlocks = 0, nListBlocks = 0;
-    static const bool noFusedLists = getenv("SNB_NO_FUSED_LISTS") != nullptr;
-    const bool fuseLists = lists != nullptr && !noFusedLists;
+    const bool fuseLists = lists != nullptr && (packed || !switches().noFusedLists);
     if (fuseLists) { q = *lists; nExclBlocks = (q.nExclAtoms + 255) / 256; nListBlocks = nExclBlocks + (q.n + 255) / 256; }
-    const size_t listLds = (fuseLists && energy) ? sizeof(double) * 2 * q.nSlices : 0;
-    dim3 gridAll(nwg + nListBlocks);
-    if (wrap) {
-        if (energy) SNB_LAUNCH_LDS((k_direct<Real, MC, true, true>), gridAll, listLds, p, q, nExclBlocks, nListBlocks);
-        else SNB_LAUNCH_LDS((k_direct<Real, MC, true, false>), gridAll, listLds, p, q, nExclBlocks, nListBlocks);
-    } else {
-        if (energy) SNB_LAUNCH_LDS((k_direct<Real, MC, false, true>), gridAll, listLds, p, q, nExclBlocks, nListBlocks);
-        else SNB_LAUNCH_LDS((k_direct<Real, MC, false, false>), gridAll, listLds, p, q, nExclBlocks, nListBlocks);
-    }
+    const size_t listLds = (fuseLists && energy) ? sizeof(double) * 2 * q.nSlices : 0;      // the energy list bodies reduce per slice in LDS
+    const dim3 gridAll(nwg + nListBlocks), block(256);
+    SNB_LAUNCH_LDS(kernel, gridAll, listLds, p, q, nExclBlocks, nListBlocks);
     return fuseLists;
 }
+// register allocation, in the hardware's units of 8 VGPRs (accumulation registers included), of the tile kernel launchDirect runs for
+// these arguments (of p: useSwitch, ewUsePoly, fixed); 16 when the runtime cannot tell
+template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int mc, bool wrap, bool energy) {
+    bool packed;
+    TileKernel<Real> kernel;
+    switch (mc) {
+        case MC_NOCUTOFF: kernel = directKernel<Real, MC_NOCUTOFF>(p, wrap, energy, &packed); break;
+        case MC_RF: kernel = directKernel<Real, MC_RF>(p, wrap, energy, &packed); break;
+        case MC_EWALD: kernel = directKernel<Real, MC_EWALD>(p, wrap, energy, &packed); break;
+        default: kernel = directKernel<Real, MC_LJPME>(p, wrap, energy, &packed); break;
+    }
+    hipFuncAttributes attr;
+    return (hipFuncGetAttributes(&attr, (const void*)kernel) == hipSuccess && attr.numRegs > 0) ? (attr.numRegs + 7) / 8 : 16;
+}
+template int directVgprUnits<float>(const DirectParams<float>&, int, bool, bool);
+template int directVgprUnits<double>(const DirectParams<double>&, int, bool, bool);
 
 // Returns true when the launch also ran the pair lists passed in `lists` (single-precision forces-only tile kernel); otherwise the
 // caller launches them itself.

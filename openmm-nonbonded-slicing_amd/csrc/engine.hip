@@ -7,6 +7,7 @@
 // ComputeContext; a handle owns plain HIP buffers and enqueues precompiled gfx950 kernels on one stream.
 #include "../../include/snb.h"
 #include "snb_internal.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -17,12 +18,24 @@
 #include <map>
 #include <numeric>
 #include <set>
+#include <thread>
 #include <tuple>
 #include <type_traits>
 
 namespace snb {
 
 static thread_local std::string g_createError;
+
+// inside a spin wait
+static inline void cpuRelax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    __asm__ __volatile__("yield");
+#else
+    std::this_thread::yield();
+#endif
+}
 
 struct HipError { std::string msg; };
 #define HIPCHECK(expr)                                                                                         \
@@ -57,8 +70,7 @@ struct PinnedRing {
     ~PinnedRing() { for (auto& s : slots) { if (s.ev) (void)hipEventDestroy(s.ev); if (s.p) (void)hipHostFree(s.p); } }
     void copy(void* dst, const void* src, size_t bytes, hipStream_t st) {
         if (bytes == 0) return;
-        static const bool direct = getenv("SNB_NO_PINNED_RING") != nullptr;      // test switch: the copy straight from the caller's array (synchronised)
-        if (direct) { HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); HIPCHECK(hipStreamSynchronize(st)); return; }
+        if (switches().noPinnedRing) { HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); HIPCHECK(hipStreamSynchronize(st)); return; }
         Slot& s = slots[next]; next = (next + 1) % SLOTS;
         if (s.pending) { HIPCHECK(hipEventSynchronize(s.ev)); s.pending = false; }
         if (s.cap < bytes) { if (s.p) (void)hipHostFree(s.p); s.p = nullptr; s.cap = std::max<size_t>(bytes, 4096); HIPCHECK(hipHostMalloc(&s.p, s.cap, hipHostMallocDefault)); }
@@ -192,11 +204,9 @@ template <typename Real> struct PmePlan {
         // Round 3, double precision (c5, 180^3 = 12 x 15 and 90^3 = 9 x 10): the register passes win on the y and z axes (y 183 -> 150 us,
         // inverse z 185 -> 134, 90^3: 32 -> 22 and 21 -> 14) and in the fused x kernel of the 90^3 mesh (63 -> 42), but the x kernel of the
         // 180^3 mesh, which also holds the spectra of all subsets, spills with 15-point transforms in double (351 -> 488): staged there.
-        bool twoPass = true;
-        if (const char* e = getenv("SNB_FFT_TWOPASS")) twoPass = atoi(e) != 0;
-        if (!twoPass) d.rx1 = d.ry1 = d.rz1 = d.rx2 = d.ry2 = d.rz2 = 0;
+        if (!switches().fftTwoPass) d.rx1 = d.ry1 = d.rz1 = d.rx2 = d.ry2 = d.rz2 = 0;
         // (round 4: the fused x kernel runs 15- / 16-point transforms in double with 256 threads and 256 registers; SNB_CONVX_STAGED_F64=1 restores the staged form)
-        if (sizeof(Real) == 8 && std::max(d.rx1, d.rx2) > 12 && getenv("SNB_CONVX_STAGED_F64")) d.rx1 = d.rx2 = 0;
+        if (sizeof(Real) == 8 && std::max(d.rx1, d.rx2) > 12 && switches().convxStagedF64) d.rx1 = d.rx2 = 0;
         gridReal.resize((size_t)nGrids * d.nx * d.ny * d.nz);
         gridCplx.resize((size_t)nGrids * d.nx * d.ny * d.nzc);
         if (sizeof(Real) == 4 && (size_t)d.nx * (d.ny | 1) * 8 <= 156 * 1024) { gridCplxB.resize((size_t)nGrids * d.nx * (d.ny + 8) * d.nzc);      // (plane path, planes that fit LDS; y padded to whole tiles of the inverse z kernel)
@@ -228,21 +238,16 @@ public:
     hipEvent_t evRebuild[3] = {nullptr, nullptr, nullptr};
     hipEvent_t evStepDone[2] = {nullptr, nullptr}; long long stepCounter = 0;      // displacement-triggered rebuilds: end-of-execute events
     hipStream_t stream2 = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr, evPairA = nullptr;
-    // measured on c3: serial 0.80 ms/step, forked 0.87 (default priority) / 1.32 (high or low priority): the graph's cross-stream
-    // dependencies cost more than the overlap returns, so the fork is opt-in
-    bool concurrentPme = getenv("SNB_CONCURRENT_PME") && atoi(getenv("SNB_CONCURRENT_PME"));
-    // Overlapped steps (round 4; the reference runs its reciprocal pipeline on a queue of its own beside the pair kernel,
+    const Switches& sw = switches();
+    // (sw.concurrentPme, the fork of forces-only graph steps, is opt-in: the graph's cross-stream dependencies cost more than the overlap returns)
+    // Overlapped steps (sw.overlap, round 4; the reference runs its reciprocal pipeline on a queue of its own beside the pair kernel,
     // CommonNonbondedSlicingKernels.cpp:520-530, 1176-1179, 1377-1380).  Graph steps run the PME chain on stream2 while a first launch of
-    // the tile kernel, held to overlapCuLimit work-groups per CU (its work-groups count themselves per physical CU and leave when the
+    // the tile kernel, held to sw.overlapCuLimit work-groups per CU (its work-groups count themselves per physical CU and leave when the
     // CU is full), runs beside it; a second launch behind the chain fills the chip.  Both launches claim their work items from one
     // device counter, so the split follows the chain's actual duration.  Eager (stamped) steps stay serial: the per-kernel timers keep
     // measuring every kernel alone.  dOverlap: [0] the counter, [16 ...] the SNB_CU_SLOTS residency counts; zeroed by the gather pass.
-    int overlapMode = getenv("SNB_OVERLAP") ? atoi(getenv("SNB_OVERLAP")) : 1;      // default on (round 4: c3 0.414 -> 0.377 ms per step with derivatives)
-    int overlapCuLimit = getenv("SNB_OVERLAP_CU_LIMIT") ? atoi(getenv("SNB_OVERLAP_CU_LIMIT")) : 2;
-    int overlapGridA = getenv("SNB_OVERLAP_GRID_A") ? atoi(getenv("SNB_OVERLAP_GRID_A")) : 0;      // 0: six work-groups per CU
-    int overlapGridB = getenv("SNB_OVERLAP_GRID_B") ? atoi(getenv("SNB_OVERLAP_GRID_B")) : 0;      // 0: four work-groups per CU
-    long long overlapMinTiles = getenv("SNB_OVERLAP_MIN_TILES") ? atoll(getenv("SNB_OVERLAP_MIN_TILES")) : 100000;      // below this the pair kernel is shorter than the PME chain and the fork only costs (c2, 65k tiles: +2 %)
-    int numCUs = 256; DevBuf<int> dOverlap, dOverlapTrace;
+    int numCUs = 256; DevBuf<int> dOverlap, dOverlapTrace; int overlapDumps = 3;
+    int pairVgprUnits[2][2];      // [per-pair wrapping][energy]: register allocation of the tile kernel a CU-limited launch runs (direct.hip directVgprUnits), resolved by the constructor
     struct EvSet { hipEvent_t e[5]; bool pending = false; KernelStamps ks; };   // start, direct0, direct1(=recip0 after pair lists), recip1, end; per-kernel stamps (snb_stats.sum_kernel_ms)
     std::vector<EvSet> ring; int ringPos = 0;
     // host-side definition
@@ -255,7 +260,7 @@ public:
     DevBuf<unsigned char> ownedPos;
     // sorted state
     int* hNbPub = nullptr; int* dNbPub = nullptr; int nbPubSeq = 0;      // the rebuild's totals in mapped host memory + sequence number (gpuRebuild)
-    // Rebuild BESIDE the steps (fixed rebuild interval; startSideBuild / finishSideBuild): `sideLead` steps before a rebuild falls due the
+    // Rebuild BESIDE the steps (fixed rebuild interval; startSideBuild / finishSideBuild): `sw.sideLead` steps before a rebuild falls due the
     // positions are copied aside and the whole GPU build runs on a stream of its own into the second set of list buffers (`shadow`), while the
     // steps go on with the list in use; when the rebuild falls due the two sets change places.  The build's small latency-bound kernels fill
     // gaps of the steps instead of standing between them (measured with a second engine as the builder, tools/async_rebuild_probe.py: 24 us
@@ -266,7 +271,7 @@ public:
     } shadow;
     hipStream_t streamBuild = nullptr; hipEvent_t evSnap = nullptr, evBuilt = nullptr, evFlagsReset = nullptr; bool flagsResetPending = false; DevBuf<unsigned char> posSnap;
     bool sortGraphSuspect = false;      // see gpuRebuild
-    bool sideMode = true, sideBuilding = false, sidePending = false; int sideLead = 3, sideSeq = 0; long long sideBuilds = 0, sideDiscarded = 0;
+    bool sideBuilding = false, sidePending = false; int sideSeq = 0; long long sideBuilds = 0, sideDiscarded = 0;
     int npadPredict = 0; long long padMispredictions = 0;      // > 0: size of the padded arrays the next GPU rebuild assumes (gpuRebuild); how often that was too small
     int Npad = 0, numBlocks = 0; int64_t numTiles = 0, numMaskTiles = 0, shardTiles = 0; bool wrapMode = false;
     std::vector<int> sortedToUser, userToSorted;
@@ -276,6 +281,12 @@ public:
     // SNB_MIXED: single-precision arithmetic, direct-space forces accumulated in 64-bit fixed point (direct.hip, fAdd) -- three arrays of
     // Npad 64-bit words (6 Npad floats, one spare), then the three reciprocal arrays: 10 Npad floats, all cleared by the gather pass
     bool fixedForces() const { return sizeof(Real) == 4 && cfg.precision == SNB_MIXED; }
+    bool useSwitch() const { return cfg.use_switch && cfg.method != SNB_NoCutoff && cfg.method != SNB_LJPME; }
+    int methodClass() const {
+        if (cfg.method == SNB_CutoffNonPeriodic || cfg.method == SNB_CutoffPeriodic) return MC_RF;
+        if (cfg.method == SNB_Ewald || cfg.method == SNB_PME) return MC_EWALD;
+        return cfg.method == SNB_LJPME ? MC_LJPME : MC_NOCUTOFF;
+    }
     int forceArrays() const { return fixedForces() ? 10 : 7; }
     void layoutForces() {
         forceBuf.resize((size_t)forceArrays() * Npad);
@@ -382,11 +393,15 @@ public:
         if (c.stream) stream = (hipStream_t)c.stream; else { HIPCHECK(hipStreamCreate(&stream)); ownStream = true; }
         ring.resize(RING);
         { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) numCUs = prop.multiProcessorCount; }
-        if (const char* e = getenv("SNB_SIDE_REBUILD")) sideMode = atoi(e) != 0;
-        if (const char* e = getenv("SNB_SIDE_LEAD")) sideLead = std::max(1, atoi(e));
-        if (overlapMode) { dOverlap.resize(SNB_OVERLAP_INTS); HIPCHECK(hipMemsetAsync(dOverlap.p, 0, sizeof(int) * SNB_OVERLAP_INTS, stream)); }
-        if (getenv("SNB_STEP_TRACE")) { dStepTrace.resize(16); HIPCHECK(hipMemsetAsync(dStepTrace.p, 0, sizeof(long long) * 16, stream)); }
-        if (overlapMode && getenv("SNB_OVERLAP_DEBUG")) { dOverlapTrace.resize(SNB_CU_SLOTS * 8); HIPCHECK(hipMemsetAsync(dOverlapTrace.p, 0xff, sizeof(int) * SNB_CU_SLOTS * 8, stream)); }
+        {      // the tile kernels a CU-limited launch can run: their allocations are asked for here, outside any capture
+            DirectParams<Real> p;
+            std::memset(&p, 0, sizeof(p));
+            p.useSwitch = useSwitch() ? 1 : 0; p.ewUsePoly = sw.ewaldErfc ? 0 : 1; p.fixed = fixedForces();
+            for (int w = 0; w < 2; w++) for (int e = 0; e < 2; e++) pairVgprUnits[w][e] = directVgprUnits<Real>(p, methodClass(), w != 0, e != 0);
+        }
+        if (sw.overlap) { dOverlap.resize(SNB_OVERLAP_INTS); HIPCHECK(hipMemsetAsync(dOverlap.p, 0, sizeof(int) * SNB_OVERLAP_INTS, stream)); }
+        if (sw.stepTrace) { dStepTrace.resize(16); HIPCHECK(hipMemsetAsync(dStepTrace.p, 0, sizeof(long long) * 16, stream)); }
+        if (sw.overlap && sw.overlapDebug) { dOverlapTrace.resize(SNB_CU_SLOTS * 8); HIPCHECK(hipMemsetAsync(dOverlapTrace.p, 0xff, sizeof(int) * SNB_CU_SLOTS * 8, stream)); }
         for (auto& r : ring) { for (int k = 0; k < 5; k++) HIPCHECK(hipEventCreate(&r.e[k])); for (int k = 0; k < 16; k++) { HIPCHECK(hipEventCreate(&r.ks.start[k])); HIPCHECK(hipEventCreate(&r.ks.stop[k])); } }
         charge.assign(N, 0.0); sigma.assign(N, 1.0); epsilon.assign(N, 0.0); subset.assign(N, 0);
         lambdas.assign((size_t)S * 2, 1.0); dispCoef.assign(S, 0.0); hostSliceE.assign((size_t)S * 2, 0.0);
@@ -423,8 +438,8 @@ public:
     }
     ~Engine() override {
         (void)hipStreamSynchronize(stream);
-        if (getenv("SNB_VERBOSE") && stats.n_rebuilds > 0) fprintf(stderr, "[snb] rebuilds: %lld, of them %lld built beside the steps; %lld side builds discarded\n", (long long)stats.n_rebuilds, sideBuilds, sideDiscarded);
-        if (dStepTrace.p && getenv("SNB_STEP_TRACE")) {      // device wall clock (100 MHz) of the last replayed step, relative to the start of its gather pass
+        if (sw.verbose && stats.n_rebuilds > 0) fprintf(stderr, "[snb] rebuilds: %lld, of them %lld built beside the steps; %lld side builds discarded\n", (long long)stats.n_rebuilds, sideBuilds, sideDiscarded);
+        if (dStepTrace.p) {      // device wall clock (100 MHz) of the last replayed step, relative to the start of its gather pass
             long long t[16] = {0}; (void)hipMemcpy(t, dStepTrace.p, sizeof(t), hipMemcpyDeviceToHost);
             auto us = [&](int k) { return t[k] ? (t[k] - t[0]) / 100.0 : -1.0; };
             fprintf(stderr, "[snb] step trace (us after the gather pass started; -1: not run): pair A %.1f .. %.1f | pair B %.1f .. %.1f | own %.1f | merge %.1f | plane %.1f | mix+z %.1f .. %.1f | interpolation %.1f .. %.1f\n",
@@ -607,7 +622,7 @@ public:
     static inline bool owns(int I, int J) { return ((I + J) & 1) ? (I > J) : (I < J); }
 
     void rebuild() {
-        static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
+        const bool verbose = sw.verbose;
         const auto tr0 = std::chrono::steady_clock::now();
         if (verbose) { HIPCHECK(hipStreamSynchronize(stream)); }      // (diagnostic only: separates the wait for the queued steps from the rebuild's own time)
         const auto tr1 = std::chrono::steady_clock::now();
@@ -985,7 +1000,7 @@ public:
         }
         if (particles) {
             // headroom of the spreader's 32-bit fixed point, per mesh: max(16, 8 x atoms per mesh cell) (misc.hip, k_fixScale)
-            static const double forced = getenv("SNB_FIX_HEADROOM") ? atof(getenv("SNB_FIX_HEADROOM")) : 0.0;      // test switch: a fixed headroom (16 = the rule before the mesh-dependent one)
+            const double forced = sw.fixHeadroom;
             auto headroom = [&](const PmePlanDims& d) { const double cells = (double)std::max(d.nx, 1) * std::max(d.ny, 1) * std::max(d.nz, 1); return forced > 0 ? forced : std::max(16.0, 8.0 * (double)N / cells); };
             launchParticleParams<Real>(N, nsub, dBaseP.p, offP.empty() ? nullptr : dOffPStart.p, dOffPGlobal.p, dOffPDelta.p, dGlobals.p, dUSubset.p, dUCharge.p, dUSigEps.p,
                                        dParamSums.p, dFixScale.p, headroom(pme.d), headroom(dpme.d), stream);
@@ -1047,23 +1062,22 @@ public:
     // SNB_NB_PUBLISH_WAIT_MS, default 2000).  The copy goes on `buildStream`, the stream the build was enqueued on, and waits for it: only
     // there is it ordered after the build's counters (a side build writes them on streamBuild, not on the live step stream)
     void waitForTotals(int seq, int* h, hipStream_t buildStream) {
-        static const int waitMs = getenv("SNB_NB_PUBLISH_WAIT_MS") ? std::max(0, atoi(getenv("SNB_NB_PUBLISH_WAIT_MS"))) : 2000;      // test switch (0: always the copy)
+        const int waitMs = sw.nbPublishWaitMs;
         volatile int* pub = hNbPub;
         if (waitMs > 0) {
             const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(waitMs);
-            while (pub[8] != seq && std::chrono::steady_clock::now() < deadline) { __builtin_ia32_pause(); }
+            while (pub[8] != seq && std::chrono::steady_clock::now() < deadline) cpuRelax();
             if (pub[8] == seq) { for (int k = 0; k < 8; k++) h[k] = pub[k]; return; }
         }
         HIPCHECK(hipMemcpyAsync(h, dCounters.p, sizeof(int) * 8, hipMemcpyDeviceToHost, buildStream));
         HIPCHECK(hipStreamSynchronize(buildStream));
-        static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
-        if (verbose) fprintf(stderr, "[snb] totals of build %d not published within %d ms: copied on the %s stream (tiles %d, work items %d + %d, overflow %d, padded %d)\n",
+        if (sw.verbose) fprintf(stderr, "[snb] totals of build %d not published within %d ms: copied on the %s stream (tiles %d, work items %d + %d, overflow %d, padded %d)\n",
                              seq, waitMs, buildStream == streamBuild ? "side-build" : "build", h[0], h[1], h[4], h[3], h[7]);
     }
     // a build whose totals are in: host-side counts, the next prediction, statistics
     void acceptBuild(const int* h, float sortMs) {
         numTiles = h[0]; numWorkItems = h[1] + h[4]; numMaskTiles = h[2]; wrapMode = false;
-        if (getenv("SNB_DEBUG_WORK")) {      // consistency of the work list: the items must cover every tile exactly once
+        if (sw.debugWork) {      // consistency of the work list: the items must cover every tile exactly once
             std::vector<int4> hw(numWorkItems);
             HIPCHECK(hipMemcpy(hw.data(), workItems.p, sizeof(int4) * numWorkItems, hipMemcpyDeviceToHost));
             long long sumZ = 0; int hist[9] = {0};
@@ -1076,8 +1090,7 @@ public:
         // next rebuild's array size: this count + 0.4 % + 8 blocks (c3: 300 k atoms move its count by a few blocks between rebuilds); never shrinking,
         // so that the buffers -- and the step graph's arguments -- stay where they are
         npadPredict = std::max(npadPredict, ((int)(h[7] * 1.004) + 256 + 31) / 32 * 32);
-        { static const int shortBy = getenv("SNB_NB_PREDICT_SHORT") ? atoi(getenv("SNB_NB_PREDICT_SHORT")) : 0;      // test switch: predict this many blocks too FEW (exercises the repeat path)
-          if (shortBy > 0) npadPredict = std::max(32, h[7] - 32 * shortBy); }
+        if (sw.nbPredictShort > 0) npadPredict = std::max(32, h[7] - 32 * sw.nbPredictShort);
         stats.n_rebuilds++;
         float gpuMs = 0;   // device time of the build (the host clock would also count the queued steps this call waited for)
         HIPCHECK(hipEventElapsedTime(&gpuMs, evRebuild[0], evRebuild[1]));
@@ -1086,17 +1099,17 @@ public:
 
     // ---- the rebuild beside the steps ----
     void swapListSets() {
-        auto sw = [](auto& a, auto& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); };
-        sw(dUserToSorted, shadow.dUserToSorted); sw(dSortedToUser, shadow.dSortedToUser); sw(atomSubset, shadow.atomSubset); sw(atomGrid, shadow.atomGrid);
-        sw(blockSubset, shadow.blockSubset); sw(tileJ, shadow.tileJ); sw(colRange, shadow.colRange); sw(posq, shadow.posq); sw(posRef, shadow.posRef);
-        sw(sigeps, shadow.sigeps); sw(imageOffset, shadow.imageOffset); sw(tileInfo, shadow.tileInfo); sw(workItems, shadow.workItems); sw(masks, shadow.masks);
+        auto exch = [](auto& a, auto& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); };
+        exch(dUserToSorted, shadow.dUserToSorted); exch(dSortedToUser, shadow.dSortedToUser); exch(atomSubset, shadow.atomSubset); exch(atomGrid, shadow.atomGrid);
+        exch(blockSubset, shadow.blockSubset); exch(tileJ, shadow.tileJ); exch(colRange, shadow.colRange); exch(posq, shadow.posq); exch(posRef, shadow.posRef);
+        exch(sigeps, shadow.sigeps); exch(imageOffset, shadow.imageOffset); exch(tileInfo, shadow.tileInfo); exch(workItems, shadow.workItems); exch(masks, shadow.masks);
     }
-    // whether the rebuild that falls due `sideLead` executes from now may be built beside the steps: a list built on the GPU with a predicted
+    // whether the rebuild that falls due `sw.sideLead` executes from now may be built beside the steps: a list built on the GPU with a predicted
     // padded count is in use, nothing but the positions has changed since, fixed interval.  (Displacement-triggered rebuilds were given side
     // builds too, timed by a guess of the watch's next interval -- built, parity green, and slower than rebuilding in line at the watch's own
     // pace: 0.3634 against 0.3539 ms per step on c3, the guess brings rebuilds forward and a third of them still came in line.  Removed.)
     bool sideBuildPossible() const {
-        return sideMode && !sidePending && gpuBuilt && cfg.rebuild_interval > sideLead + 1 && cfg.neighbor_padding > 0 && isPeriodic() && !cfg.host_neighbor_build && !cfg.disable_graph
+        return sw.sideRebuild && !sidePending && gpuBuilt && cfg.rebuild_interval > sw.sideLead + 1 && cfg.neighbor_padding > 0 && isPeriodic() && !cfg.host_neighbor_build && !cfg.disable_graph
                && !needRebuild && !paramsDirty && !staticDirty && !valuesDirty && !excValuesDirty && npadPredict > 0 && npadPredict == Npad && hNbPub && dNbPub && devUserPos;
     }
     // Copies the positions aside (in stream order: the positions of the step just enqueued) and enqueues the whole build on streamBuild, into
@@ -1106,7 +1119,7 @@ public:
             int lo = 0, hi = 0;
             HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
             // (normal priority: at the lowest the build crawls and the steps end up waiting for it, at the highest its kernels push the tile kernel aside)
-            HIPCHECK(hipStreamCreateWithPriority(&streamBuild, hipStreamNonBlocking, getenv("SNB_SIDE_PRIO_HIGH") ? hi : (getenv("SNB_SIDE_PRIO_LOW") ? lo : (lo + hi) / 2)));
+            HIPCHECK(hipStreamCreateWithPriority(&streamBuild, hipStreamNonBlocking, sw.sidePrioHigh ? hi : (sw.sidePrioLow ? lo : (lo + hi) / 2)));
             HIPCHECK(hipEventCreateWithFlags(&evSnap, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evBuilt, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evFlagsReset, hipEventDisableTiming));
         }
         const size_t bytes = (size_t)N * (posStride4 ? 4 : 3) * (posIsDouble ? 8 : 4);
@@ -1126,7 +1139,7 @@ public:
         sideBuilding = false; stream = liveStream; devUserPos = livePos; swapListSets();
         if (!ok) { colCells[0] = liveCells[0]; colCells[1] = liveCells[1]; HIPCHECK(hipEventSynchronize(evBuilt)); }      // (whatever was enqueued has finished with the scratch arrays)
         sidePending = ok;
-        { static const bool verbose = getenv("SNB_VERBOSE") != nullptr; if (verbose && ok) fprintf(stderr, "[snb] side build started after execute %lld\n", stepCounter - 1); }
+        if (sw.verbose && ok) fprintf(stderr, "[snb] side build started after execute %lld\n", stepCounter - 1);
     }
     // drops a pending side build (its result will not be used): waits until it has finished with the scratch arrays
     void cancelSideBuild() {
@@ -1141,9 +1154,8 @@ public:
         int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         waitForTotals(sideSeq, h, streamBuild);      // (a fallback copy must wait for the side build, not for the live steps)
         HIPCHECK(hipEventSynchronize(evBuilt));      // (returns at once: the totals are the build's last kernel but one)
-        static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
-        static const bool reject = getenv("SNB_SIDE_REJECT") != nullptr;      // test switch: every side build is discarded and the rebuild repeated in line
-        if (h[7] < N || (h[7] & 31) || h[7] > Npad || h[3] != 0 || reject) {
+        const bool verbose = sw.verbose;
+        if (h[7] < N || (h[7] & 31) || h[7] > Npad || h[3] != 0 || sw.sideReject) {
             if (verbose) fprintf(stderr, "[snb] side rebuild discarded (padded count %d of %d, overflow flag %d): rebuilding in line\n", h[7], Npad, h[3]);
             if (h[7] > Npad) { npadPredict = 0; padMispredictions++; }
             sideDiscarded++;
@@ -1163,9 +1175,8 @@ public:
 
     bool gpuRebuild() {
         if (cfg.method == SNB_NoCutoff || N < 64) return false;
-        if (sideBuilding && !(npadPredict > 0 && npadPredict == Npad && getenv("SNB_NB_SYNC_PADDED") == nullptr)) return false;
-        static const bool hostTriclinic = getenv("SNB_HOST_TRICLINIC") != nullptr;      // testing aid: old behaviour
-        if (hostTriclinic && (!isPeriodic() || !(box[3] == 0 && box[6] == 0 && box[7] == 0))) return false;
+        if (sideBuilding && !(npadPredict > 0 && npadPredict == Npad && !sw.nbSyncPadded)) return false;
+        if (sw.hostTriclinic && (!isPeriodic() || !(box[3] == 0 && box[6] == 0 && box[7] == 0))) return false;
         const double R = cfg.cutoff + cfg.neighbor_padding;
         // The cell the builder works in: the periodic box, or -- CutoffNonPeriodic -- a rectangular cell around the atoms' bounding box with
         // more than a list radius of empty margin on every side, so that no periodic image of anything is ever in reach
@@ -1221,7 +1232,7 @@ public:
         for (int d = 0; d < 3; d++) p.origin[d] = origin[d];
         for (int i = 0; i < 9; i++) tileCell[i] = box[i];
         p.listCutoff = (float)R;
-        { static const bool bw = getenv("SNB_NB_BOX_WALK") != nullptr; p.boxWalk = bw ? 1 : 0; }
+        p.boxWalk = sw.nbBoxWalk ? 1 : 0;
         p.jumpDist = (float)(2.0 * std::sqrt(2.0) * std::max(box[0] / ncx, box[4] / ncy));   // neighbours along the sort path of a dense region are closer than this
         p.uSubset = dUSubset.p; p.uCharge = dUCharge.p; p.uSigEps = dUSigEps.p; p.uExclStart = exclStart.p; p.uExclList = exclList.p;
         p.slotOfSubset = dSlotOfSubset.p;
@@ -1240,7 +1251,7 @@ public:
             static_assert(std::is_trivially_copyable<SortKey>::value, "SortKey is compared bytewise");
             SortKey key; std::memset(&key, 0, sizeof(key));
             key.p = p; key.pos = devUserPos; key.isDouble = posIsDouble; key.stride4 = posStride4; key.temp = dSortTemp.p; key.tempBytes = tempBytes;
-            static const bool noSortGraph = getenv("SNB_NO_SORT_GRAPH") != nullptr;
+            const bool noSortGraph = sw.noSortGraph;
             bool replayed = false;
             // (round 4: a replayed phase-A graph once left 32 N padded slots -- its memset node for blockWideOut had stopped zeroing after other
             // graphs with memset nodes had been instantiated; phase A now zero-fills with a kernel, misc.hip launchZeroFill.  `sortGraphSuspect`
@@ -1275,8 +1286,7 @@ public:
         // rebuild on the arrays are sized by the previous count plus a margin (a few spare all-padding blocks at the end) and the build
         // goes on without waiting; the exact count comes back with the tile counters below, and an overflow (k_nbScatter counts the
         // atoms that did not fit) repeats the rebuild with the exact count.  Saves one host round trip (~75 us) per rebuild.
-        static const bool noPredict = getenv("SNB_NB_SYNC_PADDED") != nullptr;      // test switch: wait for the count, as before round 4
-        const bool predicted = npadPredict > 0 && !noPredict;
+        const bool predicted = npadPredict > 0 && !sw.nbSyncPadded;
         if (predicted) Npad = npadPredict;
         else {
             int npadDev = 0;
@@ -1300,13 +1310,12 @@ public:
             tileJ.resize(tileCap * 32); tileInfo.resize(tileCap); masks.resize(tileCap * 32); workItems.resize(2 * (tileCap / 4 + 2 * numBlocks + 64)); workItemsStage.resize(tileCap / 4 + 2 * numBlocks + 64); workItemsPartial.resize(tileCap / 4 + 2 * numBlocks + 64);
             p.nPadded = Npad; p.nBlocks = numBlocks; p.blockSubset = blockSubset.p;
             p.shardBegin = shardBegin; p.shardWidth = shardEnd - shardBegin; p.shardPeriod = shardPeriod;
-            { static const bool boxOnly = getenv("SNB_BOX_PRUNE") != nullptr; p.exactPrune = boxOnly ? 0 : 1; }
-            { static const int it = getenv("SNB_ITEM_TILES") ? std::max(1, std::min(32, atoi(getenv("SNB_ITEM_TILES")))) : 8; p.itemTiles = it; }
+            p.exactPrune = sw.boxPrune ? 0 : 1; p.itemTiles = sw.itemTiles;
             p.blockCenter = dBlockCenter.p; p.blockHalf = dBlockHalf.p;
             p.sortedToUser = dSortedToUser.p; p.userToSorted = dUserToSorted.p; p.posq = posq.p; p.sigeps = sigeps.p; p.imageOffset = imageOffset.p;
             p.atomSubset = atomSubset.p; p.atomGrid = atomGrid.p; p.colRange = colRange.p; p.zIndex = dZIndex.p;
             dAtomCell.resize(Npad); p.atomCell = dAtomCell.p;
-            static const bool nbTrace = getenv("SNB_NB_TRACE") != nullptr;
+            const bool nbTrace = sw.nbTrace;
             if (nbTrace) { dNbTrace.resize((size_t)4 * numBlocks); p.dbgOut = dNbTrace.p; }
             p.tileJ = tileJ.p; p.tileInfo = tileInfo.p; p.masks = masks.p; p.workItems = workItems.p; p.workItemsStage = workItemsStage.p; p.workItemsPartial = workItemsPartial.p; p.counters = dCounters.p;
             p.tileCapacity = (int)tileCap; p.workCapacity = (int)(tileCap / 4 + 2 * numBlocks + 64); p.maskCapacity = (int)tileCap;
@@ -1321,8 +1330,7 @@ public:
             int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             // the totals come back through mapped host memory and a sequence number the host spins on (a sleeping hipStreamSynchronize wakes
             // up 30-45 us after the kernel has ended, with the GPU idle); the synchronisation behind it then returns at once
-            static const bool noSpin = getenv("SNB_NB_NO_SPIN") != nullptr;
-            if (hNbPub && dNbPub && !noSpin) {
+            if (hNbPub && dNbPub && !sw.nbNoSpin) {
                 const int seq = ++nbPubSeq;
                 launchNeighborPublish(dCounters.p, dNbPub, seq, stream);
                 waitForTotals(seq, h, stream);
@@ -1335,13 +1343,13 @@ public:
             // from plain launches before anything is sized by it)
             if (!sortGraphSuspect && stats.n_rebuilds > 0 && h[7] > 2 * std::max(Npad, N) && !sideBuilding) {
                 sortGraphSuspect = true;
-                { static const bool verbose = getenv("SNB_VERBOSE") != nullptr; if (verbose) fprintf(stderr, "[snb] rebuild: padded count %d after %d: phase A once more without its graph\n", h[7], Npad); }
+                if (sw.verbose) fprintf(stderr, "[snb] rebuild: padded count %d after %d: phase A once more without its graph\n", h[7], Npad);
                 return gpuRebuild();
             }
             if (predicted && (h[7] > Npad || h[7] < N || (h[7] & 31))) {      // the prediction was too small (or the count is inconsistent): once more, waiting for the exact count
                 if (h[7] < N || (h[7] & 31)) throw HipError{"neighbour build: inconsistent padded atom count"};
                 npadPredict = 0; padMispredictions++;
-                { static const bool verbose = getenv("SNB_VERBOSE") != nullptr; if (verbose) fprintf(stderr, "[snb] rebuild: padded count %d exceeded the predicted %d, repeating with the exact count (%lld so far)\n", h[7], Npad, (long long)padMispredictions); }
+                if (sw.verbose) fprintf(stderr, "[snb] rebuild: padded count %d exceeded the predicted %d, repeating with the exact count (%lld so far)\n", h[7], Npad, (long long)padMispredictions);
                 return gpuRebuild();
             }
             if (nbTrace && h[3] == 0) {
@@ -1361,7 +1369,7 @@ public:
                 fprintf(stderr, "[snb] nb trace: last block start %.1f us after the first\n", lastStart / 100.0);
             }
             if (h[3] == 0) { acceptBuild(h, sortMs); gpuBuilt = true; needRebuild = false; paramsDirty = false; stepsSinceRebuild = 0; (void)t0; return true; }
-            if (getenv("SNB_VERBOSE")) fprintf(stderr, "[snb] gpu neighbour build attempt %d: tiles %d work %d masks %d overflow %d partial %d maxPartTiles %d maxPartWork %d (cap %zu, region %zu / %zu)\n", attempt, h[0], h[1], h[2], h[3], h[4], h[5], h[6], tileCap, tileCap / 64, (tileCap / 4 + 2 * numBlocks + 64) / 64);
+            if (sw.verbose) fprintf(stderr, "[snb] gpu neighbour build attempt %d: tiles %d work %d masks %d overflow %d partial %d maxPartTiles %d maxPartWork %d (cap %zu, region %zu / %zu)\n", attempt, h[0], h[1], h[2], h[3], h[4], h[5], h[6], tileCap, tileCap / 64, (tileCap / 4 + 2 * numBlocks + 64) / 64);
             // capacity: a partition (1/64 of the arrays) ran out of tiles, masks or work items -> grow and retry
             if ((size_t)h[5] > tileCap / 64 || (size_t)h[6] > (tileCap / 4 + 2 * numBlocks + 64) / 64) { tileCap = std::max((size_t)h[5] * 64 * 5 / 4, tileCap * 3 / 2) + 4096; continue; }
             return false;   // a block gathered more than its LDS list holds, or a block is too extended for tile images: host path
@@ -1373,7 +1381,7 @@ public:
     void fillPme(PmeParams<Real>& p, PmePlan<Real>& plan, bool wantEnergy) {
         p.d = plan.d; p.nsub = nGrids; p.natoms = Npad; p.posq = posq.p; p.sigeps = sigeps.p; p.atomSubset = atomSubset.p; p.atomGrid = atomGrid.p;
         p.cells = pmeCells.p;
-        { static const bool tr = getenv("SNB_PME_TRACE") != nullptr; if (tr) { if (!dPmeTrace.p) { dPmeTrace.resize(8); HIPCHECK(hipMemset(dPmeTrace.p, 0, 64)); } p.trace = dPmeTrace.p; } }
+        if (sw.pmeTrace) { if (!dPmeTrace.p) { dPmeTrace.resize(8); HIPCHECK(hipMemset(dPmeTrace.p, 0, 64)); } p.trace = dPmeTrace.p; }
         p.stepTrace = (traceThisStep && plan.dispersion == (cfg.method == SNB_LJPME)) ? dStepTrace.p : nullptr;      // (the step's LAST mesh: its inverse z transform is what the second launch follows)
         p.cellsReady = (!plan.dispersion && cellsFromGather) ? 1 : 0;
         p.fixDev = dFixScale.p ? dFixScale.p + (plan.dispersion ? 2 : 0) : nullptr;      // (k_fixScale keeps it in step with the parameters)
@@ -1385,7 +1393,7 @@ public:
         for (int i = 0; i < 9; i++) { p.recip[i] = (Real)r[i]; p.recipLo[i] = (Real)(r[i] - (double)p.recip[i]); }
         p.alpha = (Real)plan.alpha; p.volume = (Real)det; p.dispersion = plan.dispersion ? 1 : 0;
         p.lambdas = dLambdas.p; p.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p; p.gridSubset = gridSubset.p; p.nsubTotal = nsub; p.mix = cfg.shard_count == 1 ? 1 : 0;
-        { static const bool m16 = getenv("SNB_MIX_16X16") != nullptr; p.mix16 = m16 ? 1 : 0; }
+        p.mix16 = sw.mix16 ? 1 : 0;
         p.sliceE = sliceE.p; p.fpx = fpx.p; p.fpy = fpy.p; p.fpz = fpz.p; p.wantEnergy = wantEnergy ? 1 : 0;
         // brick kernels: the sort columns were cut for the Coulomb mesh; any mesh whose cells tile those columns can use them,
         // with bricks of `group` columns when one column is narrower than 5 cells (stencil 4 + 1 cell of drift)
@@ -1393,7 +1401,7 @@ public:
         p.zSlabs = 1;
         // measured on c3: f64 accumulation 1 slab 110 us, 2 slabs 105 us, 4 slabs 145 us; fixed-point (single precision, even nz) 1 slab 61 us, 2 slabs 67 us
         if (plan.d.nz % 2 == 0 && plan.d.nz >= 32 && !(sizeof(Real) == 4)) p.zSlabs = 2;
-        if (const char* zs = getenv("SNB_ZSLABS")) { const int k = atoi(zs); if (k >= 1 && plan.d.nz % k == 0) p.zSlabs = k; }
+        if (sw.zSlabs >= 1 && plan.d.nz % sw.zSlabs == 0) p.zSlabs = sw.zSlabs;
         int ncx, ncy, gx, gy;
         if (brickGeometry(plan, ncx, ncy, gx, gy)) {
             p.sortNcx = ncx; p.sortNcy = ncy; p.groupX = gx; p.groupY = gy; p.colRange = colRange.p;
@@ -1407,8 +1415,8 @@ public:
     bool brickGeometry(const PmePlan<Real>& plan, int& ncx, int& ncy, int& gx, int& gy) const {
         if (colCells[0] <= 0) return false;
         ncx = pme.d.nx / colCells[0]; ncy = pme.d.ny / colCells[1];
-        static const int gMin = getenv("SNB_BRICK_GROUP") ? atoi(getenv("SNB_BRICK_GROUP")) : 1;
-        auto group = [](int n, int ncols) { if (n % ncols) return 0; const int cpc = n / ncols; for (int g = gMin; g <= 4; g++) if (g * cpc >= 5 && ncols % g == 0) return g; return 0; };
+        const int gMin = sw.brickGroup;
+        auto group = [gMin](int n, int ncols) { if (n % ncols) return 0; const int cpc = n / ncols; for (int g = gMin; g <= 4; g++) if (g * cpc >= 5 && ncols % g == 0) return g; return 0; };
         gx = group(plan.d.nx, ncx); gy = group(plan.d.ny, ncy);
         const bool packable = plan.d.nx < 1024 && plan.d.ny < 1024 && plan.d.nz < 1024;   // k_pmeCells packs 10 bits per axis
         return packable && gx > 0 && gy > 0 && sizeof(double) * (size_t)(gx * plan.d.nx / ncx) * (gy * plan.d.ny / ncy) * plan.d.nz <= 100 * 1024;
@@ -1438,15 +1446,14 @@ public:
                              (box[3] * box[7] - box[4] * box[6]) * sc, -box[0] * box[7] * sc, box[0] * box[4] * sc};
         const double perNmX = plan.d.nx * std::sqrt(r[0] * r[0] + r[3] * r[3] + r[6] * r[6]), perNmY = plan.d.ny * std::sqrt(r[1] * r[1] + r[4] * r[4] + r[7] * r[7]);      // mesh cells per nm of displacement
         int M = std::max(1, (int)std::ceil(0.5 * std::max(cfg.neighbor_padding, 0.0) * std::max(perNmX, perNmY) + 0.01));
-        if (const char* e = getenv("SNB_SPREAD_MARGIN")) M = std::max(0, atoi(e));      // test switch (0: every border crossing becomes a stray)
-        static const bool noFixed = getenv("SNB_NO_FIXED_SPREAD") != nullptr;
-        const bool fixed = sizeof(Real) == 4 && !noFixed;
+        if (sw.spreadMargin >= 0) M = sw.spreadMargin;
+        const bool fixed = sizeof(Real) == 4 && !sw.noFixedSpread;
         const size_t accBytes = fixed ? 4 : 8;
         const int cx = gx * (plan.d.nx / ncx), cy = gy * (plan.d.ny / ncy), nz = plan.d.nz;
         const int RX = cx + 4 + 2 * M, RY = cy + 4 + 2 * M;
         if (RX > plan.d.nx || RY > plan.d.ny || gx * gy > 16 || nz > 256) return;
         int best = 0;
-        static const int forced = getenv("SNB_OWN_SLABS") ? atoi(getenv("SNB_OWN_SLABS")) : 0;
+        const int forced = sw.ownSlabs;
         for (int pass = 0; pass < 2 && !best; pass++)
             for (int k = 2; k <= 32; k++) {      // (at least two: a single slab's region, nz + 4 planes, would wrap onto itself)
                 if (forced > 0 && k != forced) continue;
@@ -1512,7 +1519,6 @@ public:
         // Forces-only steps replay a captured hipGraph (the ~14 small launches of a step are host-launch-bound otherwise:
         // 7-8 us of idle GPU between kernels).  Every 32nd step -- and every energy step -- is enqueued eagerly with HIP events
         // around the pair kernel and the reciprocal pipeline; those samples feed snb_stats' kernel timers.
-        static const bool noStepGraph = getenv("SNB_NO_STEP_GRAPH") != nullptr;      // measurement aid: every step as plain launches
         // (the step right after a rebuild goes out as plain launches: the GPU is idle at that point -- the rebuild ended with a host
         // read-back -- and capturing + instantiating the step graph first would keep it idle for another ~50 us; the capture then happens
         // at the next step, while this one is executing)
@@ -1541,8 +1547,7 @@ public:
         const GraphKey stepKey{devUserPos, posIsDouble, posStride4, includeDirect != 0, includeRecip != 0, energy ? (energySelective ? 2 : 1) : 0, outPtr, outIsDouble, outAccumulate};
         bool haveGraph = false;
         for (auto& g : graphs) if (g.key == stepKey && g.exec) haveGraph = true;
-        static const bool eagerRebuildSteps = getenv("SNB_EAGER_REBUILD_STEP") != nullptr;      // test switch: the rebuild step as plain launches (rounds 1-3)
-        const bool eager = cfg.disable_graph || noStepGraph || (rebuilding && (!haveGraph || eagerRebuildSteps)) || (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0);      // (no timed step while a list is being built beside it: the kernel timers are for kernels running alone)
+        const bool eager = cfg.disable_graph || sw.noStepGraph || (rebuilding && (!haveGraph || sw.eagerRebuildStep)) || (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0);      // (no timed step while a list is being built beside it: the kernel timers are for kernels running alone)
         if (eager) {
             EvSet& ev = ring[ringPos]; ringPos = (ringPos + 1) % RING;
             if (ev.pending) harvest(ev);
@@ -1554,10 +1559,10 @@ public:
             CachedGraph* cached = nullptr;
             for (auto& g : graphs) if (g.key == key) { cached = &g; if (!g.stale) graphExec = g.exec; break; }
             if (!graphExec) {
-                if (!stream2 && (concurrentPme || overlapMode)) {   // created outside the capture
+                if (!stream2 && (sw.concurrentPme || sw.overlap)) {   // created outside the capture
                     int lo = 0, hi = 0;
                     HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-                    HIPCHECK(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, getenv("SNB_PME_PRIO_LOW") ? lo : (getenv("SNB_PME_PRIO_HIGH") ? hi : (lo + hi) / 2)));
+                    HIPCHECK(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, sw.pmePrioLow ? lo : (sw.pmePrioHigh ? hi : (lo + hi) / 2)));
                     HIPCHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evPairA, hipEventDisableTiming));
                 }
                 hipGraph_t graph = nullptr;
@@ -1568,8 +1573,7 @@ public:
                 HIPCHECK(hipStreamEndCapture(stream, &graph));
                 const auto tc1 = std::chrono::steady_clock::now();
                 bool updated = false;
-                static const bool noUpdate = getenv("SNB_NO_GRAPH_UPDATE") != nullptr;      // test switch: a new instantiation after every rebuild, as before round 4
-                if (cached && cached->exec && !noUpdate) {
+                if (cached && cached->exec && !sw.noGraphUpdate) {
                     hipGraphNode_t errNode = nullptr; hipGraphExecUpdateResult res;
                     if (hipGraphExecUpdate(cached->exec, graph, &errNode, &res) == hipSuccess) { graphExec = cached->exec; cached->stale = false; updated = true; }
                     else (void)hipGetLastError();
@@ -1581,20 +1585,18 @@ public:
                     else { (void)hipGraphExecDestroy(graphs[graphVictim].exec); graphs[graphVictim] = {key, graphExec, false}; graphVictim = (graphVictim + 1) % MAX_GRAPHS; }
                 }
                 HIPCHECK(hipGraphDestroy(graph));
-                { static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
-                  if (verbose) fprintf(stderr, "[snb] step graph: capture %.0f us, %s %.0f us (host)\n", std::chrono::duration<double, std::micro>(tc1 - tc0).count(), updated ? "update" : "instantiate",
-                                       std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tc1).count()); }
+                if (sw.verbose) fprintf(stderr, "[snb] step graph: capture %.0f us, %s %.0f us (host)\n", std::chrono::duration<double, std::micro>(tc1 - tc0).count(), updated ? "update" : "instantiate",
+                                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tc1).count());
             }
-            { static const bool verbose = getenv("SNB_VERBOSE") != nullptr;
-              if (verbose && rebuilding) {
-                  const auto tl0 = std::chrono::steady_clock::now();
-                  HIPCHECK(hipGraphLaunch(graphExec, stream));
-                  const auto tl1 = std::chrono::steady_clock::now();
-                  HIPCHECK(hipStreamSynchronize(stream));
-                  fprintf(stderr, "[snb] rebuild step: graph launch %.0f us (host), step done after %.0f us\n", std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
-                          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl0).count());
-              } else HIPCHECK(hipGraphLaunch(graphExec, stream)); }
-            if (overlapMode && dOverlap.p) { static int dbg = getenv("SNB_OVERLAP_DEBUG") ? 3 : 0; if (dbg > 0) { dbg--; dumpOverlapTable(); } }
+            if (sw.verbose && rebuilding) {
+                const auto tl0 = std::chrono::steady_clock::now();
+                HIPCHECK(hipGraphLaunch(graphExec, stream));
+                const auto tl1 = std::chrono::steady_clock::now();
+                HIPCHECK(hipStreamSynchronize(stream));
+                fprintf(stderr, "[snb] rebuild step: graph launch %.0f us (host), step done after %.0f us\n", std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
+                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl0).count());
+            } else HIPCHECK(hipGraphLaunch(graphExec, stream));
+            if (sw.overlapDebug && sw.overlap && dOverlap.p && overlapDumps > 0) { overlapDumps--; dumpOverlapTable(); }
         }
         }      // forces step
         if (autoMode && cfg.neighbor_padding > 0) {
@@ -1603,8 +1605,8 @@ public:
             HIPCHECK(hipEventRecord(ev, stream));
         }
         stepCounter++;
-        // the rebuild that falls due sideLead executes from now starts here, beside the steps, from the positions of the step just enqueued
-        if (!autoMode && stepsSinceRebuild == cfg.rebuild_interval - sideLead && sideBuildPossible()) startSideBuild();
+        // the rebuild that falls due sw.sideLead executes from now starts here, beside the steps, from the positions of the step just enqueued
+        if (!autoMode && stepsSinceRebuild == cfg.rebuild_interval - sw.sideLead && sideBuildPossible()) startSideBuild();
         if (energy) {
             energyPending = true;
             if (energyOut) { fetchSliceEnergies(); double e = 0; for (int i = 0; i < 2 * S; i++) e += lambdas[i] * hostSliceE[i]; *energyOut = e; }      // (synchronises)
@@ -1657,7 +1659,7 @@ public:
         const bool graphStep = !ev && fmode == StepForces::Full;      // (replayed forces steps: the only ones that overlap, fork or trace)
         void* const out = fmode == StepForces::Full ? outPtr : nullptr;
         if (ev) for (int k = 0; k < 16; k++) ev->ks.used[k] = false;
-        static const bool noStamps = getenv("SNB_NO_KERNEL_STAMPS") != nullptr;      // measurement aid: only the pair-kernel / pipeline timers
+        const bool noStamps = sw.noKernelStamps;
         // (a stamped launch completes a signal of its own: ~8 us per kernel, 70 us per step with every PME kernel stamped -- measured: 20-step
         // region 0.484 ms per step against 0.467 without them.  Every third eager step carries the per-kernel stamps, starting with the
         // first one after snb_reset_timers; the pair-kernel and pipeline timers keep every eager step.)
@@ -1685,7 +1687,7 @@ public:
         }
         if (energy && Npad > 0) { gc.clearE = sliceE.p; gc.nClearE = S * 2 * SNB_SLICE_E_PARTS; }
         if (includeRecip && isPme() && dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
-        if (graphStep && overlapMode && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
+        if (graphStep && sw.overlap && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
         traceThisStep = graphStep && dStepTrace.p != nullptr;      // (SNB_STEP_TRACE; replayed steps only: the stamps of the last one are printed when the engine is destroyed)
         gc.stepTrace = traceThisStep ? dStepTrace.p : nullptr;
         launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream);
@@ -1693,9 +1695,9 @@ public:
         const bool ew = cfg.method >= SNB_Ewald;
         // Opt-in (SNB_CONCURRENT_PME=1): forces-only graph steps run the reciprocal pipeline on a second stream beside the pair
         // kernel (disjoint force arrays fx.. / fpx..).  Timed (eager) steps stay serial so the per-kernel event timers stay clean.
-        // overlapped step (see overlapMode above): any graph step with both halves; needs the GPU-built work list (static item order is irrelevant)
-        const bool overlap = graphStep && overlapMode && includeDirect && includeRecip && isPme() && nGrids > 0 && stream2 && dOverlap.p && numWorkItems > 0 && shardTiles >= overlapMinTiles;
-        const bool fork = overlap || (graphStep && !energy && includeDirect && includeRecip && isPme() && nGrids > 0 && concurrentPme && stream2);
+        // overlapped step (see sw.overlap above): any graph step with both halves; needs the GPU-built work list (static item order is irrelevant)
+        const bool overlap = graphStep && sw.overlap && includeDirect && includeRecip && isPme() && nGrids > 0 && stream2 && dOverlap.p && numWorkItems > 0 && shardTiles >= sw.overlapMinTiles;
+        const bool fork = overlap || (graphStep && !energy && includeDirect && includeRecip && isPme() && nGrids > 0 && sw.concurrentPme && stream2);
         hipStream_t pmeStream = stream;
         if (fork) {
             HIPCHECK(hipEventRecord(evFork, stream));
@@ -1737,28 +1739,25 @@ public:
             for (int i = 0; i < 14; i++) p.ewPolyE[i] = (Real)ewPolyE[i];
             for (int i = 0; i < 21; i++) p.dispPoly[i] = (Real)dispPoly[i];
             p.ewScale = (Real)(2.0 / ewR2Max);
-            { static const bool noPoly = getenv("SNB_EWALD_ERFC") != nullptr; p.ewUsePoly = noPoly ? 0 : 1; }
+            p.ewUsePoly = sw.ewaldErfc ? 0 : 1;
             const double ic2 = 1.0 / (cfg.cutoff * cfg.cutoff), ic6 = ic2 * ic2 * ic2;
             const double dar2 = cfg.alpha_d * cfg.alpha_d * cfg.cutoff * cfg.cutoff;
             p.invCut6 = (Real)ic6; p.multShift6 = (Real)(ic6 * (1.0 - std::exp(-dar2) * (1.0 + dar2 + 0.5 * dar2 * dar2)));
-            const bool sw = cfg.use_switch && cfg.method != SNB_NoCutoff && cfg.method != SNB_LJPME;
-            p.useSwitch = sw ? 1 : 0; p.switchDist = (Real)cfg.switch_distance;
-            p.invSwitchWidth = (Real)(sw ? 1.0 / (cfg.cutoff - cfg.switch_distance) : 0.0);
+            p.useSwitch = useSwitch() ? 1 : 0; p.switchDist = (Real)cfg.switch_distance;
+            p.invSwitchWidth = (Real)(useSwitch() ? 1.0 / (cfg.cutoff - cfg.switch_distance) : 0.0);
             for (int i = 0; i < 9; i++) p.box[i] = (Real)(gpuBuilt ? tileCell[i] : box[i]);
             if (isPeriodic()) { p.invBoxDiag[0] = (Real)(1.0 / box[0]); p.invBoxDiag[1] = (Real)(1.0 / box[4]); p.invBoxDiag[2] = (Real)(1.0 / box[8]); }
             p.boxDiag[0] = (Real)box[0]; p.boxDiag[1] = (Real)box[4]; p.boxDiag[2] = (Real)box[8];
-            int mc = MC_NOCUTOFF;
-            if (cfg.method == SNB_CutoffNonPeriodic || cfg.method == SNB_CutoffPeriodic) mc = MC_RF;
-            else if (cfg.method == SNB_Ewald || cfg.method == SNB_PME) mc = MC_EWALD;
-            else if (cfg.method == SNB_LJPME) mc = MC_LJPME;
-            static const bool noFuse = getenv("SNB_NO_FUSED_LISTS") != nullptr;
+            const int mc = methodClass();
+            const bool noFuse = sw.noFusedLists;
             p.stepTrace = traceThisStep ? dStepTrace.p : nullptr; p.traceSlot = 2;
-            if (overlap) {      // first launch: resident beside the reciprocal pipeline, at most overlapCuLimit work-groups per CU
-                p.workCounter = dOverlap.p; p.cuSlots = dOverlap.p + SNB_WORK_SHARDS * 32; p.cuLimit = overlapCuLimit;
-                { static const bool byCount = getenv("SNB_OVERLAP_BY_COUNT") != nullptr; p.cuBaseMax = byCount ? -1 : 0x7fffffff; }      // (0x7fffffff: the launcher fills in the kernel's own allocation)
-                p.gridCap = overlapGridA > 0 ? overlapGridA : 6 * numCUs; p.listsLast = 1;
+            if (overlap) {      // first launch: resident beside the reciprocal pipeline, at most sw.overlapCuLimit work-groups per CU
+                p.workCounter = dOverlap.p; p.cuSlots = dOverlap.p + SNB_WORK_SHARDS * 32; p.cuLimit = sw.overlapCuLimit;
+                p.cuBaseMax = sw.overlapByCount ? -1 : 0x7fffffff;
+                p.gridCap = sw.overlapGridA > 0 ? sw.overlapGridA : 6 * numCUs; p.listsLast = 1;
                 p.cuTrace = dOverlapTrace.p;      // (SNB_OVERLAP_DEBUG; null otherwise)
                 directB = p; directMc = mc;
+                if (!sw.overlapByCount && p.cuLimit > 0) p.cuBaseMax = (p.cuLimit - 1) * pairVgprUnits[wrapMode][energy];      // its resident work-groups sit below (cuLimit - 1) allocations of this kernel
             }
             if (!forces) { if (launchDirectEnergy<Real>(p, mc, wrapMode, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true; }
             else if (launchDirect<Real>(p, mc, wrapMode, energy, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true;
@@ -1773,10 +1772,10 @@ public:
                 std::memset(&pp, 0, sizeof(pp));
                 // the interpolation of the step's last mesh also writes the user-order force (no k_finishForces launch): unsharded, brick path,
                 // reciprocal work on the step's own stream (the pair kernel's accumulators are complete by then)
-                static const bool noFuse = getenv("SNB_NO_FUSED_FINISH") != nullptr;
+                const bool noFuse = sw.noFusedFinish;
                 // (an overlapped step keeps the fused finish: its last interpolation waits for both launches of the tile kernel)
                 const bool canFinish = out && (!fork || overlap) && !noFuse && cfg.shard_count == 1;
-                static const bool noFusedE = getenv("SNB_NO_FUSED_ENERGY_FINISH") != nullptr;      // test switch: k_finishSliceEnergies as a kernel of its own
+                const bool noFusedE = sw.noFusedEnergyFinish;
                 auto withOutput = [&](PmeParams<Real>& q, bool last) {
                     q.outForces = (canFinish && last) ? out : nullptr; q.outIsDouble = outIsDouble; q.outAccumulate = outAccumulate;
                     q.finOut = nullptr;
@@ -1788,7 +1787,7 @@ public:
                 // and the last interpolation -- which also delivers the step's forces -- follows both.
                 auto beforeLastInterpolation = [&]() {
                     if (!overlap) return;
-                    directB.cuSlots = nullptr; directB.cuLimit = 0; directB.listsLast = 0; directB.traceSlot = 4; directB.gridCap = overlapGridB > 0 ? overlapGridB : 4 * numCUs;
+                    directB.cuSlots = nullptr; directB.cuLimit = 0; directB.listsLast = 0; directB.traceSlot = 4; directB.gridCap = sw.overlapGridB > 0 ? sw.overlapGridB : 4 * numCUs;
                     bool t = false;
                     launchDirect<Real>(directB, directMc, wrapMode, energy, nullptr, stream2, nullptr, nullptr, &t);
                     HIPCHECK(hipStreamWaitEvent(stream2, evPairA, 0));
@@ -1997,6 +1996,7 @@ snb_status snb_create(const snb_config* cfg, snb_handle* out) {
     // the caller agrees on the step itself and calls snb_rebuild_neighbors on every rank)
     if (cfg->shard_count > 1 && cfg->rebuild_interval < 0) { g_createError = "rebuild_interval < 0 (displacement-triggered rebuilds) is not available with shard_count > 1"; return SNB_ERR_UNSUPPORTED; }
     try {
+        (void)switches();      // the environment is read here, once per process, before anything touches the GPU
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_createError = "hip: no HIP device available (the engine has no CPU fallback)"; return SNB_ERR_HIP; }
         if (cfg->device < 0 || cfg->device >= ndev) { g_createError = "invalid device ordinal"; return SNB_ERR_INVALID_ARGUMENT; }

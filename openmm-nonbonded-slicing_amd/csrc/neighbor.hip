@@ -16,7 +16,7 @@ namespace snb {
 
 // Periodic cell in OpenMM's reduced form: a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz), |bx| <= ax/2, |cx| <= ax/2, |cy| <= by/2.
 struct Lattice { float ax, bx, by, cx, cy, cz; };
-template <typename P> __device__ inline bool getenvBoxWalk(const P& p) { return p.boxWalk != 0; }      // SNB_NB_BOX_WALK=1: the round-2 candidate walk (test switch)
+template <typename P> __device__ inline bool useBoxWalk(const P& p) { return p.boxWalk != 0; }      // SNB_NB_BOX_WALK=1: the round-2 candidate walk (test switch)
 template <typename Real> __device__ inline Lattice latticeOf(const NbParams<Real>& p) {
     return Lattice{(float)p.boxm[0], (float)p.boxm[3], (float)p.boxm[4], (float)p.boxm[6], (float)p.boxm[7], (float)p.boxm[8]};
 }
@@ -399,7 +399,7 @@ template <typename Real> __global__ __launch_bounds__(256, 4) void k_nbBuildTile
     const Lattice Lt = latticeOf(p);
     const float X0 = cxx - hx - R, X1 = cxx + hx + R, Y0 = cyy - hy - R, Y1 = cyy + hy + R, Z0 = czz - hz - R, Z1 = czz + hz + R;
     const float feps = 1e-5f;                             // fractional slack for float-vs-double rounding of column / bucket borders
-    const bool rectCell = Lt.bx == 0.f && Lt.cx == 0.f && Lt.cy == 0.f && !getenvBoxWalk(p);
+    const bool rectCell = Lt.bx == 0.f && Lt.cx == 0.f && Lt.cy == 0.f && !useBoxWalk(p);
     // The lattice images that can reach the grown box, with their column rectangles and fractional z ranges: geometry only, so it is
     // worked out once per block and reused for every j-subset (typically 1-4 of the 27 images survive).
     int (*imgI)[5] = s_imgI[wid]; float (*imgF)[2] = s_imgF[wid];

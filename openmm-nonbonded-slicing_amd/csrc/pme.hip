@@ -16,6 +16,7 @@
 //    evaluation and the convolution run in one kernel without leaving LDS: 5 grid passes instead of 8;
 //  * the real axis (z) is transformed with the imaginary half implied, writing nz/2+1 complex outputs.
 #include "snb_internal.h"
+#include "switches.h"
 #include <cstdlib>
 #include <type_traits>
 #include <algorithm>
@@ -409,15 +410,13 @@ template <typename Real> static int launchSpreadOwn(const PmeParams<Real>& p, hi
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s) {
     if (p.sortNcx > 0 && p.colRange != nullptr) {
         const int cx = p.groupX * (p.d.nx / p.sortNcx), cy = p.groupY * (p.d.ny / p.sortNcy);
-        static const bool noFixed = getenv("SNB_NO_FIXED_SPREAD") != nullptr;      // test switch: f64 LDS accumulation in single precision too
-        const bool fixed = std::is_same<Real, float>::value && !noFixed && p.d.nz % 2 == 0 && (p.d.nz / p.zSlabs) % 2 == 0;
+        const bool fixed = std::is_same<Real, float>::value && !switches().noFixedSpread && p.d.nz % 2 == 0 && (p.d.nz / p.zSlabs) % 2 == 0;
         const size_t accBytes = fixed ? sizeof(int) : sizeof(double);
         const size_t brickBytes = (accBytes * (size_t)cx * cy * (p.d.nz / p.zSlabs) + 15) & ~(size_t)15;
         const size_t listBytes = sizeof(int) * (fixed ? 8192 : 4096);
         const int nbz = (cx * cy + 1) / 2;
         const size_t fftBytes = sizeof(Cx<Real>) * ((size_t)2 * p.d.nz * (nbz + 1) + p.d.nz);
-        static const bool noFuse = getenv("SNB_NO_FUSED_Z") != nullptr;
-        const bool fuse = !noFuse && p.zSlabs == 1 && brickBytes + std::max(listBytes, fftBytes) <= 64 * 1024;
+        const bool fuse = !switches().noFusedZ && p.zSlabs == 1 && brickBytes + std::max(listBytes, fftBytes) <= 64 * 1024;
         const size_t lds = brickBytes + (fuse ? std::max(listBytes, fftBytes) : listBytes);
         const int nblocks = p.nsub * (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY) * p.zSlabs;
         if (!p.cellsReady) hipLaunchKernelGGL((k_pmeCells<Real>), dim3((p.natoms + 255) / 256), dim3(256), 0, s, p);
@@ -1720,7 +1719,7 @@ template <int R1, int R2, int NT> __global__ __launch_bounds__(NT) void k_fftZIn
 // threads per work-group of the y FFT pass: 512 over the same LDS tile (two rounds of register sub-transforms become one and twice the
 // waves hide the tile's load latency: 24.4 -> 22.4 us per pass on c3; SNB_FFT_THREADS=256 restores the narrower groups).  The z pass
 // was measured the other way round (16.9 us with 256 threads, 20.9 with 512) and keeps 256.
-static int fftyThreads() { static const int n = getenv("SNB_FFT_THREADS") ? atoi(getenv("SNB_FFT_THREADS")) : 512; return n == 256 ? 256 : 512; }
+static int fftyThreads() { return switches().fftThreads; }
 template <typename Real, bool FWD> static void launchFftZ(int r1, int r2, dim3 grid, size_t lds, hipStream_t s, const PmeParams<Real>& p, int NL) {
 #define X(A, B) if (r1 == A && r2 == B) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZ<Real, FWD, A, B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); SNB_STAMPED_LAUNCH(stampSlot(p, FWD ? 2 : 6), (k_fftZ<Real, FWD, A, B>), grid, dim3(256), lds, s, p, NL); return; }
     SNB_FFT_PAIRS(X)
@@ -1768,8 +1767,7 @@ template <typename Real> static void launchConvolveX(int r1, int r2, dim3 grid, 
 #define SNB_PLANE_PAIRS(X) X(6, 7) X(6, 9) X(8, 8) X(8, 10) X(9, 10) X(8, 12) X(10, 10) X(9, 12) X(10, 12) X(8, 16)
 // square plane with a split that has a kernel of its own (static splits: no calls, one table of roots); everything else takes the run-time kernel
 static bool planeSquare(const PmePlanDims& d) {
-    static const bool dyn = getenv("SNB_PLANE_DYNAMIC") != nullptr;      // measurement aid: the run-time-split kernel on square planes too
-    if (dyn || d.nx != d.ny || d.px1 != d.py1 || d.px2 != d.py2) return false;
+    if (switches().planeDynamic || d.nx != d.ny || d.px1 != d.py1 || d.px2 != d.py2) return false;
 #define X(A, B) if (d.px1 == A && d.px2 == B) return true;
     SNB_PLANE_PAIRS(X)
 #undef X
@@ -1777,16 +1775,14 @@ static bool planeSquare(const PmePlanDims& d) {
 }
 template <typename Real> static size_t planeLds(const PmeParams<Real>& p) { return sizeof(Cx<Real>) * ((size_t)p.d.nx * (p.d.ny | 1) + p.d.nx + (planeSquare(p.d) ? 0 : p.d.ny)); }
 template <typename Real> static bool planePathOK(const PmeParams<Real>& p) {
-    static const bool off = getenv("SNB_NO_PLANE_FFT") != nullptr;      // test switch: the three-kernel y / x / y pipeline
-    static const bool noRect = getenv("SNB_NO_RECT_PLANES") != nullptr; // test switch: rectangular planes on the three-pass pipeline, as before round 4
-    if (off || !std::is_same<Real, float>::value || !p.planeB || !p.planeEterm) return false;
+    if (switches().noPlaneFft || !std::is_same<Real, float>::value || !p.planeB || !p.planeEterm) return false;
     if ((p.d.ny & 1) || p.d.px1 <= 0 || p.d.py1 <= 0 || p.d.px1 * p.d.px2 != p.d.nx || p.d.py1 * p.d.py2 != p.d.ny) return false;
     if (p.nsub > 8 || planeLds(p) > 156 * 1024) return false;
-    return planeSquare(p.d) || !noRect;
+    return planeSquare(p.d) || !switches().noRectPlanes;
 }
 // y lines per work-group of the inverse z kernel = tile of the convolved planes' layout (c4, 8 subsets: plane + z kernel 45.5 + 55.0 us with 8, 61.2 + 42.4 with 4: 32-byte runs in the plane kernel's store)
 static int planeTileY(const PmeParams<float>& p) {
-    static const int env = getenv("SNB_ZMIX_NBY") ? atoi(getenv("SNB_ZMIX_NBY")) : 0;
+    const int env = switches().zmixNby;
     return (env == 2 || env == 4 || env == 8) ? env : 8;
 }
 static void launchPlaneXY(const PmeParams<float>& p, hipStream_t s) {
@@ -1802,7 +1798,7 @@ static void launchPlaneXY(const PmeParams<float>& p, hipStream_t s) {
         SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<0, 0, 1024, true>), grid, dim3(1024), lds, s, p, NBY);
         return;
     }
-    static const int nt = getenv("SNB_PLANE_NT") ? atoi(getenv("SNB_PLANE_NT")) : 1024;      // threads per plane: 1024 or 768
+    const int nt = switches().planeNt;
     if (!planeSquare(p.d)) {      // rectangular plane: the kernel with run-time splits
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<0, 0, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<0, 0, 1024>), grid, dim3(1024), lds, s, p, NBY);
@@ -1826,7 +1822,7 @@ static void launchFftZInvMix(const PmeParams<float>& p, hipStream_t s) {
 #undef X
     const size_t lds = sizeof(Cx<float>) * ((size_t)(twoPass ? 1 : 2) * p.d.nz * (NBY * NP + 1) + p.d.nz);      // (in place with a two-pass split)
     const dim3 grid((unsigned)(p.d.nx * ((p.d.ny + NBY - 1) / NBY)));
-    static const int ntEnv = getenv("SNB_ZMIX_NT") ? atoi(getenv("SNB_ZMIX_NT")) : 0;
+    const int ntEnv = switches().zmixNt;
     const bool wide = ntEnv ? ntEnv == 512 : NBY * NP >= 24;      // 24+ complex transforms per work-group (5-8 subsets): 512 threads
 #define X(A, B) if (p.d.rz1 == A && p.d.rz2 == B) { \
         if (wide) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZInvMix<A, B, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -1862,13 +1858,11 @@ template void launchPmePlanePath<double>(const PmeParams<double>&, hipStream_t);
 // own-atoms spreader: k_spreadOwn over (brick, slab) work-groups, then k_spreadMerge per brick (fused with the forward z FFT when its
 // buffers fit LDS).  Geometry (slabs, margin) and the buffers come from the engine (sized at rebuild time).
 template <typename Real> static int launchSpreadOwn(const PmeParams<Real>& p, hipStream_t s) {
-    static const bool off = getenv("SNB_NO_OWN_SPREAD") != nullptr;      // test switch: the scanning brick spreader
-    if (off || p.ownSlabs < 2 || !p.ownPartial || p.d.nz > 256) return -1;      // (one slab's region of nz + 4 planes would wrap onto itself)
-    static const bool noFixed = getenv("SNB_NO_FIXED_SPREAD") != nullptr;
+    if (switches().noOwnSpread || p.ownSlabs < 2 || !p.ownPartial || p.d.nz > 256) return -1;      // (one slab's region of nz + 4 planes would wrap onto itself)
     const int cx = p.groupX * (p.d.nx / p.sortNcx), cy = p.groupY * (p.d.ny / p.sortNcy);
     const int sz = p.d.nz / p.ownSlabs;
     if (sz & 1) return -1;      // (the regions are copied 8 or 16 bytes at a time)
-    const bool fixed = std::is_same<Real, float>::value && !noFixed;
+    const bool fixed = std::is_same<Real, float>::value && !switches().noFixedSpread;
     const int RX = cx + 4 + 2 * p.ownMargin, RY = cy + 4 + 2 * p.ownMargin, RZ = sz + 4;
     const size_t ldsOwn = (fixed ? sizeof(int) : sizeof(double)) * (size_t)RX * RY * (fixed ? ownLineStride<true>(RZ) : ownLineStride<false>(RZ));
     const int M = p.ownMargin;
@@ -1879,14 +1873,13 @@ template <typename Real> static int launchSpreadOwn(const PmeParams<Real>& p, hi
     const int nbricks = p.nsub * (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY);
     const int nb = (cx * cy + 1) / 2;
     const size_t ldsFft = sizeof(Cx<Real>) * ((size_t)2 * p.d.nz * (nb + 1) + p.d.nz);
-    static const bool noFuse = getenv("SNB_NO_FUSED_Z") != nullptr;
-    const bool fuse = !noFuse && ldsFft <= 120 * 1024;
+    const bool fuse = !switches().noFusedZ && ldsFft <= 120 * 1024;
     const int plane = (fuse && planePathOK<Real>(p)) ? 1 : 0;      // plane-major spectrum for k_planeXY
 #define SNB_OWN(FX) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spreadOwn<Real, FX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOwn); \
                       SNB_STAMPED_LAUNCH(stampSlot(p, 1), (k_spreadOwn<Real, FX>), dim3(nbricks * p.ownSlabs), dim3(512), ldsOwn, s, p); }
     // a long mesh in double precision gives a 256-thread work-group a dozen 16-byte chunks per thread, each three rounds of dependent loads
     // (c5, 180^3: 309 us): 512 threads there
-    static const int mergeNt = getenv("SNB_MERGE_NT") ? atoi(getenv("SNB_MERGE_NT")) : 0;      // test switch: 256 / 512 threads per brick
+    const int mergeNt = switches().mergeNt;
     const bool wideMerge = mergeNt ? mergeNt == 512 : (size_t)cx * cy * (p.d.nz / chunk) > 6 * 256;
 #define SNB_MERGE(FX, FZ, A, B) { if (wideMerge) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spreadMerge<Real, FX, FZ, A, B, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FZ ? ldsFft : 0)); \
                                       SNB_STAMPED_LAUNCH(stampSlot(p, 2), (k_spreadMerge<Real, FX, FZ, A, B, 512>), dim3(nbricks), dim3(512), (FZ ? ldsFft : 0), s, p, chunk, plane); } \
@@ -1952,8 +1945,7 @@ template <typename Real> void launchPmeForwardFFT(const PmeParams<Real>& p, hipS
     }
     // y
     {
-        static const int nbEnv = getenv("SNB_FFTY_NB") ? atoi(getenv("SNB_FFTY_NB")) : 0;   // measured on c3: 8: 40 us, 16: 31, 21: 28.4, 32: 27.8
-        const int NB = fftyBatch<Real>(ny, nzc, nbEnv);
+        const int NB = fftyBatch<Real>(ny, nzc, switches().fftyNb);
         const size_t lds = (size_t)2 * ny * NB * sizeof(Cx<Real>) + (size_t)ny * sizeof(Cx<Real>);
         const int tilesPerA = (nzc + NB - 1) / NB;
         launchFftStrided<Real>(p.d.ry1, p.d.ry2, dim3((unsigned)(p.nsub * nx * tilesPerA)), lds, s, p, ny, (size_t)ny * nzc, nzc, (size_t)nzc, NB, tilesPerA, -1, 1);
@@ -1967,7 +1959,7 @@ template <typename Real> void launchPmeConvolution(const PmeParams<Real>& p, hip
     const size_t twBytes = (size_t)nx * sizeof(Cx<Real>);
     // columns per work-group: 8 adjacent (ky,kz) columns are one 64-byte line per (subset, kx) row -- measured on c3 (4 subsets):
     // NB = 4: 68 us, 5: 64, 7: 69, 8: 48.5, 16: 60.5 -- so 8 when that fits ~72 KB of LDS, else 4, 2, 1
-    static const int ldsKB = getenv("SNB_CONV_LDS_KB") ? atoi(getenv("SNB_CONV_LDS_KB")) : 72;
+    const int ldsKB = switches().convLdsKB;
     int NB = 8;
     while (NB > 1 && perCol * NB > (size_t)ldsKB * 1024) NB >>= 1;
     const size_t lds = perCol * NB + twBytes;
@@ -1977,8 +1969,7 @@ template <typename Real> void launchPmeConvolution(const PmeParams<Real>& p, hip
 template <typename Real> void launchPmeInverseFFT(const PmeParams<Real>& p, hipStream_t s) {
     const int nx = p.d.nx, ny = p.d.ny, nz = p.d.nz, nzc = p.d.nzc;
     {
-        static const int nbEnv = getenv("SNB_FFTY_NB") ? atoi(getenv("SNB_FFTY_NB")) : 0;   // measured on c3: 8: 40 us, 16: 31, 21: 28.4, 32: 27.8
-        const int NB = fftyBatch<Real>(ny, nzc, nbEnv);
+        const int NB = fftyBatch<Real>(ny, nzc, switches().fftyNb);
         const size_t lds = (size_t)2 * ny * NB * sizeof(Cx<Real>) + (size_t)ny * sizeof(Cx<Real>);
         const int tilesPerA = (nzc + NB - 1) / NB;
         launchFftStrided<Real>(p.d.ry1, p.d.ry2, dim3((unsigned)(p.nsub * nx * tilesPerA)), lds, s, p, ny, (size_t)ny * nzc, nzc, (size_t)nzc, NB, tilesPerA, +1, 1);
@@ -2316,7 +2307,7 @@ template <typename Real> static bool launchInterpolateBricks(const PmeParams<Rea
     PmeParams<Real> p = p0;
     {
         const int cx = p.groupX * (p.d.nx / p.sortNcx), cy = p.groupY * (p.d.ny / p.sortNcy);
-        static const int zsEnv = getenv("SNB_INTERP_ZSLABS") ? atoi(getenv("SNB_INTERP_ZSLABS")) : 0;
+        const int zsEnv = switches().interpZSlabs;
         int zSlabs = 1;      // measured on c3: 1 slab 52 us, 2 slabs 70, 4 slabs 72 (every slab rescans the columns' atoms)
         if (zsEnv > 0 && p.d.nz % zsEnv == 0 && p.d.nz / zsEnv >= 8) zSlabs = zsEnv;
         auto ldsFor = [&](int slabs) { return ((sizeof(Real) * (size_t)(cx + 6) * (cy + 6) * (p.d.nz / slabs + 4) + 15) & ~(size_t)15) + sizeof(double) * p.nsubTotal * (p.nsubTotal + 1); };
@@ -2331,13 +2322,12 @@ template <typename Real> static bool launchInterpolateBricks(const PmeParams<Rea
             for (int k = 2; k <= 6 && nb1 * zSlabs < 192; k++) if (p.d.nz % k == 0 && p.d.nz / k >= 10) zSlabs = k;
         }
         const size_t lds = ldsFor(zSlabs);
-        static const bool noBrick = getenv("SNB_NO_INTERP_BRICKS") != nullptr;   // testing aid: force the 32-lanes-per-atom kernel
-        if (lds <= 150 * 1024 && !noBrick && p.nsubTotal * p.groupX * p.groupY <= 256) {
+        if (lds <= 150 * 1024 && !switches().noInterpBricks && p.nsubTotal * p.groupX * p.groupY <= 256) {
             const int nblocks = (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY) * zSlabs;
             if (!p.mix) p.outForces = nullptr;      // (sharded engines visit an atom once per held grid: the separate finish pass stays)
             // 512-thread work-groups go two to a CU when the brick fits LDS twice (the kernel's ~100 VGPRs allow 16 waves per CU either way):
             // with more bricks than CUs the second round of 1024-thread groups runs half empty
-            static const int ntEnv = getenv("SNB_INTERP_THREADS") ? atoi(getenv("SNB_INTERP_THREADS")) : 0;
+            const int ntEnv = switches().interpThreads;
             const bool narrow = ntEnv ? ntEnv == 512 : (nblocks > 256 && lds <= 76 * 1024);
             if (narrow) {
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2360,7 +2350,7 @@ template <typename Real> bool launchPmeInterpolate(const PmeParams<Real>& p, hip
         // The kernel needs ~100 VGPRs, so one 1024-thread work-group occupies a CU: with more bricks than CUs the launch runs in rounds.
         // Wider bricks (2 x 1, 2 x 2 columns) cut the count below the CU count and the halo overhead with it, as long as LDS allows.
         PmeParams<Real> q = p;
-        static const int gEnv = getenv("SNB_INTERP_GROUP") ? atoi(getenv("SNB_INTERP_GROUP")) : -1;
+        const int gEnv = switches().interpGroup;
         // (measured on c3, 400 single-column bricks: 1024 threads on 2 x 1-column bricks 35.2 us, 1024 threads on single columns 39.3,
         // 512 threads on single columns -- two work-groups per CU -- 29.1: when the single-column brick fits LDS twice, do not widen)
         const size_t single = sizeof(Real) * (size_t)(q.groupX * (q.d.nx / q.sortNcx) + 6) * (q.groupY * (q.d.ny / q.sortNcy) + 6) * (q.d.nz + 4) + 1024;

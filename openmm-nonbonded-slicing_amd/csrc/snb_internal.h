@@ -271,6 +271,7 @@ void launchNeighborPublish(const int* counters, int* hostMapped, int seq, hipStr
 // ---- launchers implemented in the .hip translation units -------------------------------------
 template <typename Real> bool launchDirect(const DirectParams<Real>& p, int methodClass, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s,
                                           hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr, bool* timed = nullptr);   // true: lists ran inside the launch
+template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int methodClass, bool wrap, bool energy);   // of the tile kernel launchDirect runs, in units of 8 registers
 template <typename Real> void launchPairLists(const PairListParams<Real>& p, bool energy, hipStream_t s);
 // include_forces == 0 steps: the slice energies of the tile kernel's tiles / of the two pair lists, no force arithmetic, no force stores
 template <typename Real> bool launchDirectEnergy(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, hipStream_t s,
