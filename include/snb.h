@@ -5,7 +5,8 @@
  * behind  NonbondedSlicing::CalcSlicedNonbondedForceKernel
  *   (openmmapi/include/NonbondedSlicingKernels.h:27-85):
  *     initialize(system, force)                      :48   -> snb_create + snb_set_particles/_exceptions/_lambdas/...
- *     execute(context, forces, energy, direct, recip):59   -> snb_set_box/_positions + snb_execute + snb_get_forces
+ *     execute(context, forces, energy, direct, recip):59   -> snb_set_box/_positions + snb_execute + snb_get_forces,
+ *                                                             or, with the context's own buffers bound (snb_bind_context): snb_set_box + snb_execute
  *     copyParametersToContext(context, force)        :66   -> snb_set_particles/_exceptions/_dispersion_coefficients
  *     getPMEParameters(alpha,nx,ny,nz)               :75   -> snb_get_pme_parameters
  *     getLJPMEParameters(alpha,nx,ny,nz)             :84   -> snb_get_ljpme_parameters
@@ -27,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SNB_ABI_VERSION 6
+#define SNB_ABI_VERSION 7
 
 typedef struct snb_engine* snb_handle;
 
@@ -211,6 +212,41 @@ snb_status snb_get_slice_energies(snb_handle h, double* out);
  * engine's lifetime. */
 snb_status snb_slice_energies_device(snb_handle h, const double** out);
 snb_status snb_synchronize(snb_handle h);
+
+/* -- context binding (ABI 7) ------------------------------------------------------------------- */
+/* The buffers of a GPU platform's context, named once: positions in the context's own (reordered) atom order, the 64-bit fixed-point
+ * force buffer every kernel of the platform adds into, the energy and energy-parameter-derivative accumulators (the reference reads
+ * cc.getPosq() and adds into cc.getLongForceBuffer(), platforms/common/src/kernels/pme.cc:381-389).  While a binding is in place a step is
+ * snb_set_box + snb_execute: the step's first kernel reads posq through the permutation, its last kernel adds the forces, the energy
+ * and the derivatives into the bound buffers -- no staging buffer, no kernel outside the replayed step graph, no host synchronisation.
+ * The pointers are fixed for the binding's life (they belong to the step graph's key); the contents change every step.  Other writers
+ * of the buffers must be ordered on snb_config.stream. */
+typedef struct {
+    const void*    posq;            /* device, [>= n_atoms][4], float or double by is_double, CONTEXT order; .w is ignored; never written */
+    const int32_t* atom_index;      /* device, [n_atoms]: atom_index[slot] = user index; a permutation of 0 .. n_atoms-1               */
+    int32_t        is_double;
+    int32_t        padded_n;        /* >= n_atoms: component stride of force_buffer                                                    */
+    int64_t*       force_buffer;    /* device, [3][padded_n], 2^32 per kJ/mol/nm, context order; ADDED to; NULL = no delivery.  A forces step
+                                     * adds (int64)(F * 2^32) (truncated, saturating) of the step's total force on the atom in slot s to
+                                     * force_buffer[d * padded_n + s], once per entry, in its last kernel; entries s >= n_atoms are never touched */
+    void*          energy_buffer;   /* device scalar (type by energy_is_double) or NULL: a step with include_energy == 1 and energy == NULL
+                                     * adds sum_s lambda_s E_s (summed in double, then converted)                                      */
+    void*          deriv_buffer;    /* device array (same type) or NULL: steps with include_energy 1 or 2 add the raw E[slice][term] to
+                                     * deriv_buffer[deriv_slot[slice][term]] (mode 2: for the slices of snb_set_energy_slices)         */
+    const int32_t* deriv_slot;      /* HOST, [n_slices][2]: slot in deriv_buffer of (slice, term), -1 = none; several entries may share a
+                                     * slot (their energies sum); copied at bind; NULL = no derivative delivery                        */
+    int32_t        energy_is_double;
+} snb_context_binding;
+/* Binds (b != NULL) or unbinds (b == NULL).  Checks padded_n >= n_atoms, posq and atom_index non-NULL, and that atom_index is a
+ * permutation (a device scan, read back: this call synchronises).  While bound the coordinates come from posq on every execute and
+ * snb_set_positions returns SNB_ERR_STATE; after an unbind the positions must be set again.  A bound force buffer takes the place of
+ * snb_set_force_output (setting one clears the other); snb_get_forces keeps working.  Sharded engines: SNB_ERR_UNSUPPORTED. */
+snb_status snb_bind_context(snb_handle h, const snb_context_binding* b);
+/* The caller has rewritten atom_index (and moved the contents of posq / force_buffer accordingly): call this before the next
+ * snb_execute.  The engine refreshes its user -> context map with one small kernel on its stream: no neighbour rebuild, no re-sort, no
+ * graph capture or update, no synchronisation; safe while a list is being built beside the steps (the build works from a user-order
+ * snapshot of the positions). */
+snb_status snb_context_order_changed(snb_handle h);
 
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

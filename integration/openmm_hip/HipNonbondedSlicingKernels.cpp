@@ -30,46 +30,25 @@ using namespace OpenMM;
 
 namespace NonbondedSlicing {
 
-// forces[N][3] (user = OpenMM atom-index order, float or double) -> OpenMM's 64-bit fixed-point force buffer, which is laid out
-// [3][paddedNumAtoms] in the CONTEXT's (reordered) atom order; atomIndex[contextSlot] = user index (HipContext::getAtomIndexArray()).
-template <typename Real>
-__global__ void addForcesToContext(const Real* __restrict__ forces, const int* __restrict__ atomIndex, unsigned long long* __restrict__ forceBuffers,
-                                   int numAtoms, int paddedNumAtoms) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= numAtoms) return;
-    const int user = atomIndex[slot];
-    const double scale = 4294967296.0;      // 0x100000000: OpenMM's fixed-point force scale
-    for (int d = 0; d < 3; d++)
-        atomicAdd(&forceBuffers[slot + d * (size_t)paddedNumAtoms], (unsigned long long)(long long)((double)forces[3 * (size_t)user + d] * scale));
-}
-
-// posq of the context (float4 or double4 per context slot; mixed precision adds posqCorrection, ignored here as the reference's own
-// single-precision kernels do) -> positions[N][4] in user order
-// dE/dlambda on the device: raw slice energies (double[S][2], snb_slice_energies_device) -> OpenMM's energy-parameter-derivative buffer
-// (one slot per derivative in the first thread's row).  binding[k] = derivative slot of (slice, term) k, or -1.
-template <typename Mixed>
-__global__ void addDerivativesToContext(const double* __restrict__ sliceEnergies, const int* __restrict__ binding, int n, Mixed* __restrict__ derivBuffer) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n && binding[k] >= 0) atomicAdd(&derivBuffer[binding[k]], (Mixed)sliceEnergies[k]);
-}
-
-template <typename Real4>
-__global__ void gatherUserPositions(const Real4* __restrict__ posq, const int* __restrict__ atomIndex, Real4* __restrict__ userPos, int numAtoms) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= numAtoms) return;
-    userPos[atomIndex[slot]] = posq[slot];
-}
-
+// The context's own buffers are bound to the engine once (snb.h, snb_bind_context): posq and the atom-index permutation in, the 64-bit
+// fixed-point force buffer, the energy buffer and the energy-parameter-derivative buffer out.  execute() then enqueues nothing of its own:
+// the engine's first kernel reads posq through the permutation, its last kernel adds into the context's buffers, all inside the replayed
+// step graph.  (Mixed precision adds posqCorrection, ignored here as the reference's own single-precision kernels do.)
 class HipCalcSlicedNonbondedForceKernel : public CalcSlicedNonbondedForceKernel {
 public:
     HipCalcSlicedNonbondedForceKernel(std::string name, const Platform& platform, HipContext& cu, const System& system)
-        : CalcSlicedNonbondedForceKernel(name, platform), cu(cu), engine(nullptr), userPos(nullptr), userForces(nullptr), derivBinding(nullptr) {}
-    ~HipCalcSlicedNonbondedForceKernel() {
-        snb_destroy(engine);
-        if (userPos) (void)hipFree(userPos);
-        if (userForces) (void)hipFree(userForces);
-        if (derivBinding) (void)hipFree(derivBinding);
-    }
+        : CalcSlicedNonbondedForceKernel(name, platform), cu(cu), engine(nullptr) {}
+    ~HipCalcSlicedNonbondedForceKernel() { snb_destroy(engine); }
+
+    // the context has re-sorted its atoms (HipContext::reorderAtoms rewrites posq, the atom-index array and the force buffer in place):
+    // the engine refreshes its user -> context map with one small kernel on the stream -- no rebuild, no synchronisation
+    class ReorderListener : public HipContext::ReorderListener {
+    public:
+        explicit ReorderListener(HipCalcSlicedNonbondedForceKernel& owner) : owner(owner) {}
+        void execute() override { check(snb_context_order_changed(owner.engine), owner.engine); }
+    private:
+        HipCalcSlicedNonbondedForceKernel& owner;
+    };
 
     void initialize(const System& system, const SlicedNonbondedForce& force) override {
         cu.setAsCurrent();
@@ -126,19 +105,28 @@ public:
             if (hasDeriv) hasDerivatives = true;
         }
         for (auto& d : derivs) cu.addEnergyParameterDerivative(d);
-        {   // device-side derivative accumulation: (slice, term) -> slot of the derivative in the context's buffer
-            const std::vector<std::string>& all = cu.getEnergyParamDerivNames();
-            std::vector<int> slot(bindings.size(), -1);
-            for (size_t k = 0; k < bindings.size(); k++)
-                if (bindings[k].hasDerivative) slot[k] = (int) (std::find(all.begin(), all.end(), bindings[k].name) - all.begin());
-            check(hipMalloc(&derivBinding, sizeof(int) * std::max<size_t>(slot.size(), 1)) == hipSuccess ? SNB_OK : SNB_ERR_HIP, nullptr);
-            check(hipMemcpy(derivBinding, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice) == hipSuccess ? SNB_OK : SNB_ERR_HIP, nullptr);
-        }
-
         readDefinition(system, force);
-        check(hipMalloc(&userPos, (size_t) numParticles * 4 * (useDouble ? 8 : 4)) == hipSuccess ? SNB_OK : SNB_ERR_HIP, nullptr);
-        check(hipMalloc(&userForces, (size_t) numParticles * 3 * (useDouble ? 8 : 4)) == hipSuccess ? SNB_OK : SNB_ERR_HIP, nullptr);
-        check(snb_set_force_output(engine, userForces, useDouble, 0), engine);
+        {   // bind the context's buffers: (slice, term) -> slot of the derivative in the context's buffer, -1 = none
+            const std::vector<std::string>& all = cu.getEnergyParamDerivNames();
+            std::vector<int32_t> slot(bindings.size(), -1);
+            for (size_t k = 0; k < bindings.size(); k++)
+                if (bindings[k].hasDerivative) slot[k] = (int32_t) (std::find(all.begin(), all.end(), bindings[k].name) - all.begin());
+            std::vector<int32_t> mask(numSlices, 0);      // the slices a derivative-only step must produce
+            for (size_t k = 0; k < bindings.size(); k++) if (bindings[k].hasDerivative) mask[k / 2] = 1;
+            if (hasDerivatives) check(snb_set_energy_slices(engine, mask.data()), engine);
+            snb_context_binding b = {};
+            b.posq = (const void*) cu.getPosq().getDevicePointer();
+            b.atom_index = (const int32_t*) cu.getAtomIndexArray().getDevicePointer();
+            b.is_double = useDouble;
+            b.padded_n = cu.getPaddedNumAtoms();
+            b.force_buffer = (int64_t*) cu.getLongForceBuffer().getDevicePointer();
+            b.energy_buffer = (void*) cu.getEnergyBuffer().getDevicePointer();
+            b.deriv_buffer = hasDerivatives ? (void*) cu.getEnergyParamDerivBuffer().getDevicePointer() : nullptr;
+            b.deriv_slot = slot.data();
+            b.energy_is_double = cu.getUseDoublePrecision() || cu.getUseMixedPrecision();
+            check(snb_bind_context(engine, &b), engine);
+            cu.addReorderListener(new ReorderListener(*this));
+        }
         paramsDirty = true;
     }
 
@@ -148,33 +136,12 @@ public:
         Vec3 a, b, c;  context.getPeriodicBoxVectors(a, b, c);
         const double box[9] = {a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]};
         check(snb_set_box(engine, box), engine);
-        // positions in user order (the engine keeps its own sorted order; OpenMM's reordering is invisible to it)
-        hipStream_t stream = cu.getCurrentStream();
-        const int blocks = (numParticles + 255) / 256;
-        const int* atomIndex = (const int*) cu.getAtomIndexArray().getDevicePointer();
-        if (useDouble) hipLaunchKernelGGL(gatherUserPositions<double4>, dim3(blocks), dim3(256), 0, stream, (const double4*) cu.getPosq().getDevicePointer(), atomIndex, (double4*) userPos, numParticles);
-        else hipLaunchKernelGGL(gatherUserPositions<float4>, dim3(blocks), dim3(256), 0, stream, (const float4*) cu.getPosq().getDevicePointer(), atomIndex, (float4*) userPos, numParticles);
-        check(snb_set_positions(engine, userPos, /*is_device=*/1, useDouble, /*stride4=*/1), engine);
-
-        double energy = 0;
-        const bool wantE = includeEnergy || hasDerivatives;          // Q4: derivatives accumulate whether or not the energy is requested
-        // energy == NULL: the step stays asynchronous (a replayed graph); the slice energies are summed on the device
-        check(snb_execute(engine, includeForces, wantE, includeDirect, includeReciprocal, includeEnergy ? &energy : nullptr), engine);
-        if (includeForces) {
-            unsigned long long* forceBuffers = (unsigned long long*) cu.getLongForceBuffer().getDevicePointer();
-            if (useDouble) hipLaunchKernelGGL(addForcesToContext<double>, dim3(blocks), dim3(256), 0, stream, (const double*) userForces, atomIndex, forceBuffers, numParticles, cu.getPaddedNumAtoms());
-            else hipLaunchKernelGGL(addForcesToContext<float>, dim3(blocks), dim3(256), 0, stream, (const float*) userForces, atomIndex, forceBuffers, numParticles, cu.getPaddedNumAtoms());
-        }
-        if (hasDerivatives) {      // dE/dlambda_k += E_raw[slice][term], added on the device: no read-back on the MD path
-            const double* sliceE = nullptr;
-            check(snb_slice_energies_device(engine, &sliceE), engine);
-            const int n = 2 * numSlices;
-            if (cu.getUseDoublePrecision() || cu.getUseMixedPrecision())
-                hipLaunchKernelGGL(addDerivativesToContext<double>, dim3((n + 63) / 64), dim3(64), 0, stream, sliceE, derivBinding, n, (double*) cu.getEnergyParamDerivBuffer().getDevicePointer());
-            else
-                hipLaunchKernelGGL(addDerivativesToContext<float>, dim3((n + 63) / 64), dim3(64), 0, stream, sliceE, derivBinding, n, (float*) cu.getEnergyParamDerivBuffer().getDevicePointer());
-        }
-        return includeEnergy ? energy : 0.0;
+        // Q4: derivatives accumulate whether or not the energy is requested (mode 2: only the slices they are bound to).  energy == NULL:
+        // the step is one replayed graph that reads cu.getPosq() and adds into the context's force, energy and derivative buffers;
+        // nothing is read back and nothing synchronises, as with the reference's own GPU kernels
+        const int mode = includeEnergy ? 1 : (hasDerivatives ? 2 : 0);
+        check(snb_execute(engine, includeForces, mode, includeDirect, includeReciprocal, nullptr), engine);
+        return 0.0;
     }
 
     void copyParametersToContext(ContextImpl& context, const SlicedNonbondedForce& force) override {
@@ -249,7 +216,6 @@ private:
 
     HipContext& cu;
     snb_handle engine;
-    void* userPos;  void* userForces;  int* derivBinding;
     std::vector<std::string> offsetGlobals;
     int numParticles = 0, numSubsets = 0, numSlices = 0, method = 0;
     bool useDouble = false, hasDerivatives = false, paramsDirty = true;

@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SNB_LIB_PATH") or os.path.join(_HERE, "libsnb_hip.so")      # (SNB_LIB_PATH: an experimental build of the same ABI, tools/ only)
-SNB_ABI_VERSION = 6
+SNB_ABI_VERSION = 7
 
 # every symbol include/snb.h declares (tests check the library exports each one)
 SYMBOLS = [
@@ -19,7 +19,7 @@ SYMBOLS = [
     "snb_set_dispersion_coefficients", "snb_compute_dispersion_coefficients", "snb_set_box", "snb_set_positions",
     "snb_rebuild_neighbors", "snb_execute", "snb_get_forces", "snb_set_force_output", "snb_set_shard_blocks", "snb_get_slice_energies", "snb_slice_energies_device", "snb_synchronize",
     "snb_get_pme_parameters", "snb_get_ljpme_parameters", "snb_get_stats", "snb_reset_timers", "snb_set_timing_interval", "snb_legal_grid_size", "snb_abi_version",
-    "snb_test_fft3d",
+    "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed",
 ]
 
 SNB_OK, SNB_ERR_INVALID_ARGUMENT, SNB_ERR_HIP, SNB_ERR_BOX_TOO_SMALL, SNB_ERR_NOT_PME, SNB_ERR_STATE, SNB_ERR_UNSUPPORTED = range(7)
@@ -45,6 +45,17 @@ class SnbStats(ctypes.Structure):
         ("sum_recip_ms", ctypes.c_double), ("sum_total_ms", ctypes.c_double), ("n_timed", ctypes.c_int64), ("n_host_rebuilds", ctypes.c_int64), ("n_list_overruns", ctypes.c_int64),
         ("sum_kernel_ms", ctypes.c_double * 16), ("n_kernel_timed", ctypes.c_int64 * 16), ("n_spread_strays", ctypes.c_int64),
     ]
+
+
+class SnbContextBinding(ctypes.Structure):
+    """snb_context_binding (ABI 7): the device buffers of a GPU platform's context, in its own atom order (include/snb.h)."""
+    _fields_ = [
+        ("posq", ctypes.c_void_p), ("atom_index", ctypes.c_void_p), ("is_double", ctypes.c_int32), ("padded_n", ctypes.c_int32),
+        ("force_buffer", ctypes.c_void_p), ("energy_buffer", ctypes.c_void_p), ("deriv_buffer", ctypes.c_void_p),
+        ("deriv_slot", ctypes.POINTER(ctypes.c_int32)), ("energy_is_double", ctypes.c_int32),
+    ]
+
+
 KERNEL_SLOTS = ("gather", "spread", "fft_z_forward", "fft_y_forward", "convolve_x", "fft_y_inverse", "fft_z_inverse", "interpolate")
 
 
@@ -91,6 +102,8 @@ def lib():
     L.snb_get_slice_energies.argtypes = [vp, dp]
     L.snb_synchronize.argtypes = [vp]
     L.snb_slice_energies_device.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p)]
+    L.snb_bind_context.argtypes = [vp, ctypes.POINTER(SnbContextBinding)]
+    L.snb_context_order_changed.argtypes = [vp]
     L.snb_get_pme_parameters.argtypes = [vp, dp, ip]
     L.snb_get_ljpme_parameters.argtypes = [vp, dp, ip]
     L.snb_get_stats.argtypes = [vp, ctypes.POINTER(SnbStats)]

@@ -85,6 +85,7 @@ class HipCalcSlicedNonbondedForceKernel:
         self.shard_rank, self.shard_count = shard_rank, shard_count
         self.stream = stream
         self.force = None
+        self._bound = None
 
     def __del__(self):
         try:
@@ -230,10 +231,43 @@ class HipCalcSlicedNonbondedForceKernel:
             self._check(self._lib.snb_set_lambdas(self._h, _dp(np.ascontiguousarray(lam))))
             self._lastLambdas = lam
 
+    # -- context binding (include/snb.h, snb_bind_context) -----------------------------------------
+    def bindContextBuffers(self, posq, atomIndex, paddedNumAtoms, forceBuffer=None, energyBuffer=None, derivBuffer=None, derivNames=None,
+                           posqIsDouble=False, energyIsDouble=True):
+        """Name the device buffers of a GPU platform's context, once: ``posq`` ([>= N][4], context order), ``atomIndex`` ([N] int32,
+        atomIndex[slot] = user index), the 64-bit fixed-point force buffer ([3][paddedNumAtoms], added to), the energy accumulator
+        (scalar) and the energy-parameter-derivative accumulator, whose entry k belongs to ``derivNames[k]``.  All are device addresses
+        (integers) valid on the engine's device; None = not delivered.  From then on ``execute`` pushes parameters and box only, adds
+        forces, energy and derivatives into those buffers on the engine's stream, reads nothing back and returns 0.0, as the reference's
+        GPU kernels do."""
+        slots = np.full((self.numSlices, 2), -1, dtype=np.int32)
+        if derivBuffer is not None:
+            index = {name: k for k, name in enumerate(derivNames or [])}
+            for (s, t), (name, hasDeriv) in self._binding.items():
+                if hasDeriv and name in index:
+                    slots[s, t] = index[name]
+        b = _capi.SnbContextBinding()
+        b.posq = posq; b.atom_index = atomIndex; b.is_double = int(bool(posqIsDouble)); b.padded_n = int(paddedNumAtoms)
+        b.force_buffer = forceBuffer; b.energy_buffer = energyBuffer; b.deriv_buffer = derivBuffer
+        b.deriv_slot = _ip(slots) if derivBuffer is not None else None
+        b.energy_is_double = int(bool(energyIsDouble))
+        self._check(self._lib.snb_bind_context(self._h, ctypes.byref(b)))
+        self._bound = b
+
+    def unbindContextBuffers(self):
+        self._check(self._lib.snb_bind_context(self._h, None))
+        self._bound = None
+
+    def contextOrderChanged(self):
+        """The context has reordered its atoms (rewritten atomIndex): call before the next execute.  One small kernel, no rebuild."""
+        self._check(self._lib.snb_context_order_changed(self._h))
+
     def _push_state(self, context):
         self._push_parameters(context.getParameters())
         box = np.ascontiguousarray(context.getPeriodicBoxVectors(), dtype=np.float64).reshape(9)
         self._check(self._lib.snb_set_box(self._h, _dp(box)))
+        if self._bound is not None:      # the coordinates come from the bound posq
+            return
         pos = context._positions
         self._check(self._lib.snb_set_positions(self._h, pos.ctypes.data_as(ctypes.c_void_p), 0, 1, 0))
 
@@ -241,6 +275,11 @@ class HipCalcSlicedNonbondedForceKernel:
     # (includeForces false: an energy-only step -- the engine evaluates no forces and keeps those of the last forces step; nothing is read back)
     def execute(self, context, includeForces, includeEnergy, includeDirect, includeReciprocal):
         self._push_state(context)
+        if self._bound is not None:
+            # bound context: everything is added into its device buffers on the engine's stream; nothing is read back, nothing synchronises
+            mode = 1 if includeEnergy else (2 if self._derivNames else 0)
+            self._check(self._lib.snb_execute(self._h, int(includeForces), mode, int(includeDirect), int(includeReciprocal), None))
+            return 0.0
         energy = ctypes.c_double(0.0)
         wantE = bool(includeEnergy) or bool(self._derivNames)
         # Q4: derivatives accumulate whether or not the energy is requested -- then only the slices they are bound to are evaluated (mode 2)

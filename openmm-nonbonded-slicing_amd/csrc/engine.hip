@@ -99,6 +99,8 @@ struct EngineBase {
     virtual void execute(int, int, int, int, double*) = 0;
     virtual void getForces(void*, int, int, int) = 0;
     virtual void setForceOutput(void*, int, int) = 0;
+    virtual void bindContext(const snb_context_binding*) = 0;
+    virtual void contextOrderChanged() = 0;
     virtual void setShardBlocks(int, int, int) = 0;
     virtual void getSliceEnergies(double*) = 0;
     virtual const double* sliceEnergiesDevice() = 0;
@@ -367,9 +369,58 @@ public:
     std::vector<int3> hKvec; DevBuf<int3> dKvec; DevBuf<Real> dCosSin;
     struct GraphKey {
         const void* pos; int isDouble, stride4; bool direct, recip; int energy; void* out; int outDouble, outAcc;      // energy: 0 forces only, 1 all slice energies, 2 selected slices
-        bool operator==(const GraphKey& o) const { return pos == o.pos && isDouble == o.isDouble && stride4 == o.stride4 && direct == o.direct && recip == o.recip && energy == o.energy && out == o.out && outDouble == o.outDouble && outAcc == o.outAcc; }
+        const void* ctxPosq = nullptr; void* ctxForce = nullptr; void* ctxEnergy = nullptr; void* ctxDeriv = nullptr; int ctxPadded = 0, ctxFlags = 0;      // the bound context's buffers (ctxFlags: 1 bound, 2 double posq, 4 double accumulators, 8 this step adds its total energy)
+        bool operator==(const GraphKey& o) const { return pos == o.pos && isDouble == o.isDouble && stride4 == o.stride4 && direct == o.direct && recip == o.recip && energy == o.energy && out == o.out && outDouble == o.outDouble && outAcc == o.outAcc
+                                                          && ctxPosq == o.ctxPosq && ctxForce == o.ctxForce && ctxEnergy == o.ctxEnergy && ctxDeriv == o.ctxDeriv && ctxPadded == o.ctxPadded && ctxFlags == o.ctxFlags; }
     };
     void* outPtr = nullptr; int outIsDouble = 0, outAccumulate = 0; bool outputWritten = false;   // snb_set_force_output
+    // Context binding (snb_bind_context): the caller's context-order buffers.  The per-step path goes straight to them -- the gather pass reads
+    // posq[userToCtx[u]], the step's last kernel adds into force / energy / deriv -- through ONE engine-owned map, user -> context slot, which
+    // depends on the context's order alone: rebuilds, re-sorts and list exchanges leave it alone, and snb_context_order_changed refreshes it with
+    // one kernel.  Rebuild-time code (extent, sort keys, the host builder's read-back, the side build's snapshot) works from a user-order copy
+    // of the positions staged when a rebuild starts (stageCtxPositions), so a list being built beside the steps does not depend on the order
+    // the context has moved on to.
+    struct CtxBinding { bool on = false; const void* posq = nullptr; const int* atomIndex = nullptr; int isDouble = 0, paddedN = 0; long long* force = nullptr; void* energy = nullptr; void* deriv = nullptr; int energyIsDouble = 0; } ctx;
+    DevBuf<int> dUserToCtx, dCtxScratch, dDerivSlot; DevBuf<unsigned char> ctxStage; DevBuf<double> dLambdas64; bool ctxAddTotal = false;
+    void stageCtxPositions(void* dst) { launchCtxStagePositions(ctx.posq, ctx.isDouble, dUserToCtx.p, N, dst, stream); }
+    void bindContext(const snb_context_binding* b) override {
+        if (!b) {
+            if (!ctx.on) return;
+            if (sidePending) cancelSideBuild();
+            ctx = CtxBinding(); devUserPos = nullptr; havePositions = false;      // (the positions must be set again)
+            return;
+        }
+        if (cfg.shard_count > 1) { err = "snb_bind_context: not available with shard_count > 1"; throw (int)SNB_ERR_UNSUPPORTED; }
+        if (!b->posq || !b->atom_index) throw HipError{"snb_bind_context: posq and atom_index must be given"};
+        if (b->padded_n < N) throw HipError{"snb_bind_context: padded_n is smaller than n_atoms"};
+        // atom_index must be a permutation: inverted into a scratch map with every out-of-range or repeated entry counted; nothing is read through
+        // the indices, and the engine's own map is replaced only when the count is zero
+        dCtxScratch.resize((size_t)N + 1);
+        launchCtxFill(dCtxScratch.p, N, -1, stream); launchCtxFill(dCtxScratch.p + N, 1, 0, stream);
+        launchCtxInvert(b->atom_index, N, dCtxScratch.p, dCtxScratch.p + N, stream);
+        int bad = 0;
+        HIPCHECK(hipMemcpyAsync(&bad, dCtxScratch.p + N, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        if (bad != 0) throw HipError{"snb_bind_context: atom_index is not a permutation of 0 .. n_atoms-1"};
+        if (sidePending) cancelSideBuild();
+        dUserToCtx.resize(std::max(N, 1));
+        if (N > 0) HIPCHECK(hipMemcpyAsync(dUserToCtx.p, dCtxScratch.p, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
+        ctx.on = true; ctx.posq = b->posq; ctx.atomIndex = b->atom_index; ctx.isDouble = b->is_double ? 1 : 0; ctx.paddedN = b->padded_n;
+        ctx.force = reinterpret_cast<long long*>(b->force_buffer); ctx.energy = b->energy_buffer; ctx.energyIsDouble = b->energy_is_double ? 1 : 0;
+        ctx.deriv = (b->deriv_buffer && b->deriv_slot) ? b->deriv_buffer : nullptr;
+        std::vector<int> slots((size_t)S * 2, -1);
+        if (ctx.deriv) for (int i = 0; i < 2 * S; i++) slots[i] = b->deriv_slot[i] < 0 ? -1 : b->deriv_slot[i];
+        dDerivSlot.upload(slots, stream);
+        dLambdas64.upload(lambdas, stream);
+        HIPCHECK(hipStreamSynchronize(stream));      // (the host vectors above may go)
+        if (ctx.force) { outPtr = nullptr; outputWritten = false; }      // a bound force buffer takes the place of snb_set_force_output
+        ctxStage.resize((size_t)std::max(N, 1) * 4 * (ctx.isDouble ? 8 : 4));
+        devUserPos = ctxStage.p; posIsDouble = ctx.isDouble; posStride4 = 1; havePositions = true;      // what rebuild-time code reads
+    }
+    void contextOrderChanged() override {
+        if (!ctx.on) { err = "snb_context_order_changed: no context is bound"; throw (int)SNB_ERR_STATE; }
+        launchCtxInvert(ctx.atomIndex, N, dUserToCtx.p, nullptr, stream);      // (every entry it writes is a slot below N, whatever atom_index holds)
+    }
     // captured step graphs, a few at a time: a caller that alternates between position (or output) buffers keeps one graph per buffer
     struct CachedGraph { GraphKey key; hipGraphExec_t exec; bool stale; };      // stale: the arguments changed (rebuild, parameters): re-captured and UPDATED in place at the next use
     std::vector<CachedGraph> graphs; size_t graphVictim = 0; long long execCount = 0;
@@ -584,6 +635,7 @@ public:
         lambdas.assign(l, l + (size_t)S * 2);
         hLambdas.assign(lambdas.begin(), lambdas.end());
         pinned.upload(dLambdas, hLambdas, stream);      // (pinned slot per in-flight update: no synchronisation per lambda change, and the next call may overwrite hLambdas)
+        if (ctx.on) pinned.upload(dLambdas64, lambdas, stream);      // (bound context: the total energy is weighted on the device, in double)
     }
     void setEnergySlices(const int32_t* m) override {
         for (int i = 0; i < S; i++) sliceNeedSel[i] = m[i] != 0;
@@ -602,6 +654,7 @@ public:
         if (changed) needRebuild = true;
     }
     void setPositions(const void* pos, int isDevice, int isDouble, int stride4) override {
+        if (ctx.on) { err = "snb_set_positions: a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
         posIsDouble = isDouble; posStride4 = stride4;
         const size_t bytes = (size_t)N * (stride4 ? 4 : 3) * (isDouble ? 8 : 4);
         if (isDevice) devUserPos = pos;
@@ -643,6 +696,7 @@ public:
 
     void hostRebuild() {
         auto t0 = std::chrono::steady_clock::now();
+        if (ctx.on) HIPCHECK(hipStreamSynchronize(stream));      // (the user-order copy of the bound positions was staged on the engine's stream)
         // 1. host copy of the user positions
         std::vector<double> hp((size_t)N * 3);
         {
@@ -1124,7 +1178,8 @@ public:
         }
         const size_t bytes = (size_t)N * (posStride4 ? 4 : 3) * (posIsDouble ? 8 : 4);
         posSnap.resize(bytes);
-        HIPCHECK(hipMemcpyAsync(posSnap.p, devUserPos, bytes, hipMemcpyDeviceToDevice, stream));
+        if (ctx.on) stageCtxPositions(posSnap.p);      // (bound context: the snapshot is taken in USER order, so the build does not depend on the context's order)
+        else HIPCHECK(hipMemcpyAsync(posSnap.p, devUserPos, bytes, hipMemcpyDeviceToDevice, stream));
         HIPCHECK(hipEventRecord(evSnap, stream));
         HIPCHECK(hipStreamWaitEvent(streamBuild, evSnap, 0));
         const hipStream_t liveStream = stream; const void* livePos = devUserPos;
@@ -1510,11 +1565,12 @@ public:
             else if (rebuilding && finishSideBuild()) rebuilding = false;
         }
         if ((valuesDirty || excValuesDirty) && !staticDirty && !rebuilding) refreshValues();
-        if (rebuilding) { if (valuesDirty || excValuesDirty) { staticDirty = true; valuesDirty = excValuesDirty = false; } rebuild(); }
+        if (rebuilding) { if (valuesDirty || excValuesDirty) { staticDirty = true; valuesDirty = excValuesDirty = false; } if (ctx.on) stageCtxPositions(ctxStage.p); rebuild(); }
         stepsSinceRebuild++;
         if (forces) outputWritten = outPtr != nullptr;      // (an energy-only step leaves the forces of the last forces step where they are)
         const bool energy = includeEnergy != 0;
         energySelective = includeEnergy == 2;      // derivative-only step: only the slices named by snb_set_energy_slices
+        ctxAddTotal = ctx.on && ctx.energy && includeEnergy == 1 && !energyOut;      // (with energy != NULL the caller takes the total on the host)
         if (forces) lastRecip = includeRecip && (isPme() || cfg.method == SNB_Ewald);
         // Forces-only steps replay a captured hipGraph (the ~14 small launches of a step are host-launch-bound otherwise:
         // 7-8 us of idle GPU between kernels).  Every 32nd step -- and every energy step -- is enqueued eagerly with HIP events
@@ -1544,7 +1600,9 @@ public:
             if (ev) ev->pending = true;
         } else {
         haveForceStep = true;
-        const GraphKey stepKey{devUserPos, posIsDouble, posStride4, includeDirect != 0, includeRecip != 0, energy ? (energySelective ? 2 : 1) : 0, outPtr, outIsDouble, outAccumulate};
+        GraphKey stepKey{devUserPos, posIsDouble, posStride4, includeDirect != 0, includeRecip != 0, energy ? (energySelective ? 2 : 1) : 0, outPtr, outIsDouble, outAccumulate};
+        if (ctx.on) { stepKey.ctxPosq = ctx.posq; stepKey.ctxForce = ctx.force; stepKey.ctxEnergy = ctx.energy; stepKey.ctxDeriv = ctx.deriv; stepKey.ctxPadded = ctx.paddedN;
+                      stepKey.ctxFlags = 1 | (ctx.isDouble ? 2 : 0) | (ctx.energyIsDouble ? 4 : 0) | (ctxAddTotal ? 8 : 0); }
         bool haveGraph = false;
         for (auto& g : graphs) if (g.key == stepKey && g.exec) haveGraph = true;
         const bool eager = cfg.disable_graph || sw.noStepGraph || (rebuilding && (!haveGraph || sw.eagerRebuildStep)) || (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0);      // (no timed step while a list is being built beside it: the kernel timers are for kernels running alone)
@@ -1657,7 +1715,14 @@ public:
         struct StampScope { StampScope(KernelStamps* k) { g_stamps = k; } ~StampScope() { g_stamps = nullptr; } };
         const bool forces = fmode != StepForces::None;
         const bool graphStep = !ev && fmode == StepForces::Full;      // (replayed forces steps: the only ones that overlap, fork or trace)
-        void* const out = fmode == StepForces::Full ? outPtr : nullptr;
+        const bool ctxForces = ctx.on && ctx.force && fmode == StepForces::Full;      // bound context: the step's last kernel adds into its fixed-point buffer
+        void* const out = fmode == StepForces::Full ? (ctxForces ? (void*)ctx.force : outPtr) : nullptr;
+        EnergyOut eo;
+        std::memset(&eo, 0, sizeof(eo));
+        if (ctx.on && energy) {
+            eo.lambdas = dLambdas64.p; eo.energy = ctxAddTotal ? ctx.energy : nullptr; eo.deriv = ctx.deriv; eo.derivSlot = dDerivSlot.p;
+            eo.need = energySelective ? dSliceNeedSel.p : nullptr; eo.isDouble = ctx.energyIsDouble;
+        }
         if (ev) for (int k = 0; k < 16; k++) ev->ks.used[k] = false;
         const bool noStamps = sw.noKernelStamps;
         // (a stamped launch completes a signal of its own: ~8 us per kernel, 70 us per step with every PME kernel stamped -- measured: 20-step
@@ -1690,7 +1755,8 @@ public:
         if (graphStep && sw.overlap && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
         traceThisStep = graphStep && dStepTrace.p != nullptr;      // (SNB_STEP_TRACE; replayed steps only: the stamps of the last one are printed when the engine is destroyed)
         gc.stepTrace = traceThisStep ? dStepTrace.p : nullptr;
-        launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream);
+        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream); }
+        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream);
         if (energy && Npad <= 0) launchZeroFill(sliceE.p, sizeof(double) * S * 2 * SNB_SLICE_E_PARTS, stream);      // (inside the step graph: a kernel, not a memset node)
         const bool ew = cfg.method >= SNB_Ewald;
         // Opt-in (SNB_CONCURRENT_PME=1): forces-only graph steps run the reciprocal pipeline on a second stream beside the pair
@@ -1778,6 +1844,7 @@ public:
                 const bool noFusedE = sw.noFusedEnergyFinish;
                 auto withOutput = [&](PmeParams<Real>& q, bool last) {
                     q.outForces = (canFinish && last) ? out : nullptr; q.outIsDouble = outIsDouble; q.outAccumulate = outAccumulate;
+                    q.userToCtx = ctxForces ? dUserToCtx.p : nullptr; q.ctxStride = ctx.paddedN; q.ctxAtomic = sw.ctxAtomicAdd ? 1 : 0; q.finE = eo;
                     q.finOut = nullptr;
                     if (canFinish && last && energy && q.mix && !noFusedE) { q.finParts = sliceE.p; q.finOut = sliceTotal.p; q.finN = 2 * S; q.fin = makeSliceFinish(includeDirect, includeRecip); }
                     q.dfx = fx.p; q.dfy = fy.p; q.dfz = fz.p; q.dfs = fstride; q.dfixed = fixedForces(); q.sortedToUser = dSortedToUser.p;
@@ -1809,12 +1876,13 @@ public:
         if (includeRecip && cfg.method == SNB_Ewald && cfg.shard_rank == 0) runEwald(energy, forces);
         if (out && !finished) {   // the step's last kernel: user-order forces into the caller's buffer (part of the graph)
             const bool recipDone = includeRecip && (isPme() || cfg.method == SNB_Ewald);
-            launchFinishForces<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), recipDone ? fpx.p : nullptr, fpy.p, fpz.p, dUserToSorted.p, N, out, outIsDouble, outAccumulate, stream);
+            if (ctxForces) launchFinishForcesCtx<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), recipDone ? fpx.p : nullptr, fpy.p, fpz.p, dUserToSorted.p, N, ctx.force, dUserToCtx.p, ctx.paddedN, sw.ctxAtomicAdd ? 1 : 0, stream);
+            else launchFinishForces<Real>(fx.p, fy.p, fz.p, fstride, fixedForces(), recipDone ? fpx.p : nullptr, fpy.p, fpz.p, dUserToSorted.p, N, out, outIsDouble, outAccumulate, stream);
         }
         if (energy) {
             const SliceFinish f = makeSliceFinish(includeDirect, includeRecip);
             if (!(finished && energyFinished))
-            launchFinishSliceEnergies(sliceE.p, sliceTotal.p, 2 * S, f, stream);
+            launchFinishSliceEnergies(sliceE.p, sliceTotal.p, 2 * S, f, eo, stream);
         }
         if (ev) HIPCHECK(hipEventRecord(ev->e[4], stream));
     }
@@ -1886,7 +1954,8 @@ public:
         }
     }
 
-    void setForceOutput(void* out, int isDouble, int accumulate) override { outPtr = out; outIsDouble = isDouble; outAccumulate = accumulate; outputWritten = false; }
+    void setForceOutput(void* out, int isDouble, int accumulate) override { if (out) ctx.force = nullptr;      // (takes the place of a bound force buffer)
+        outPtr = out; outIsDouble = isDouble; outAccumulate = accumulate; outputWritten = false; }
     void getForces(void* out, int isDevice, int isDouble, int accumulate) override {
         if (isDevice && out == outPtr && isDouble == outIsDouble && outputWritten) return;   // the last execute already delivered them there
         const size_t bytes = (size_t)N * 3 * (isDouble ? 8 : 4);
@@ -2050,6 +2119,8 @@ snb_status snb_get_forces(snb_handle h, void* out, int32_t isDevice, int32_t isD
 }
 snb_status snb_set_shard_blocks(snb_handle h, int32_t begin, int32_t end, int32_t period) { return guard(h, [&] { h->impl->setShardBlocks(begin, end, period); }); }
 snb_status snb_set_force_output(snb_handle h, void* out, int32_t isDouble, int32_t acc) { return guard(h, [&] { h->impl->setForceOutput(out, isDouble, acc); }); }
+snb_status snb_bind_context(snb_handle h, const snb_context_binding* b) { return guard(h, [&] { h->impl->bindContext(b); }); }
+snb_status snb_context_order_changed(snb_handle h) { return guard(h, [&] { h->impl->contextOrderChanged(); }); }
 snb_status snb_get_slice_energies(snb_handle h, double* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getSliceEnergies(out); }); }
 snb_status snb_slice_energies_device(snb_handle h, const double** out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { *out = h->impl->sliceEnergiesDevice(); }); }
 snb_status snb_synchronize(snb_handle h) { return guard(h, [&] { h->impl->sync(); }); }

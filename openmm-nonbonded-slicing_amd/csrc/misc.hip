@@ -8,7 +8,9 @@ namespace snb {
 // posq[s].xyz = userPos[sortedToUser[s]] + imageOffset[s]; charge (.w) is kept.  Padding slots (sortedToUser < 0)
 // keep their parked far-away coordinates.  The same pass clears the six force arrays of the atom (no separate memset node in the
 // step graph) and, when a Coulomb mesh is given, writes the atom's packed mesh cell for the brick spreader (pme.hip, k_pmeCells).
-template <typename Real, typename In>
+// CTX (bound context, snb_bind_context): userPos is the context's posq, [..][4] records in context order, fetched as one 16- or 32-byte
+// load through user -> context slot.
+template <typename Real, typename In, bool CTX>
 __global__ void k_gatherPositions(const In* __restrict__ userPos, int stride, const int* __restrict__ sortedToUser,
                                   const Real* __restrict__ imageOffset, typename Vec<Real>::T4* __restrict__ posq, int nPadded,
                                   Real* __restrict__ forces, int nClear, const GatherCells<Real> gc) {
@@ -24,9 +26,14 @@ __global__ void k_gatherPositions(const In* __restrict__ userPos, int stride, co
     const int u = sortedToUser[s];
     if (u < 0) { if (gc.cells) gc.cells[s] = -1; return; }
     auto v = posq[s];
+    if constexpr (CTX) {
+        const auto c = reinterpret_cast<const typename Vec<In>::T4*>(userPos)[gc.userToCtx[u]];
+        v.x = (Real)c.x + imageOffset[3 * s]; v.y = (Real)c.y + imageOffset[3 * s + 1]; v.z = (Real)c.z + imageOffset[3 * s + 2];
+    } else {
     v.x = (Real)userPos[(size_t)u * stride] + imageOffset[3 * s];
     v.y = (Real)userPos[(size_t)u * stride + 1] + imageOffset[3 * s + 1];
     v.z = (Real)userPos[(size_t)u * stride + 2] + imageOffset[3 * s + 2];
+    }
     posq[s] = v;
     if (gc.posRef) {
         const auto r0 = gc.posRef[s];
@@ -51,8 +58,13 @@ void launchGatherPositions(const void* userPos, int isDouble, int stride4, const
     if (nPadded <= 0) return;
     dim3 grid((nPadded + 255) / 256), block(256);
     const int stride = stride4 ? 4 : 3;
-    if (isDouble) SNB_STAMPED_LAUNCH(0, (k_gatherPositions<Real, double>), grid, block, 0, s, (const double*)userPos, stride, sortedToUser, imageOffset, posq, nPadded, forces, nClear, gc);
-    else SNB_STAMPED_LAUNCH(0, (k_gatherPositions<Real, float>), grid, block, 0, s, (const float*)userPos, stride, sortedToUser, imageOffset, posq, nPadded, forces, nClear, gc);
+    if (gc.userToCtx) {
+        if (isDouble) SNB_STAMPED_LAUNCH(0, (k_gatherPositions<Real, double, true>), grid, block, 0, s, (const double*)userPos, 4, sortedToUser, imageOffset, posq, nPadded, forces, nClear, gc);
+        else SNB_STAMPED_LAUNCH(0, (k_gatherPositions<Real, float, true>), grid, block, 0, s, (const float*)userPos, 4, sortedToUser, imageOffset, posq, nPadded, forces, nClear, gc);
+        return;
+    }
+    if (isDouble) SNB_STAMPED_LAUNCH(0, (k_gatherPositions<Real, double, false>), grid, block, 0, s, (const double*)userPos, stride, sortedToUser, imageOffset, posq, nPadded, forces, nClear, gc);
+    else SNB_STAMPED_LAUNCH(0, (k_gatherPositions<Real, float, false>), grid, block, 0, s, (const float*)userPos, stride, sortedToUser, imageOffset, posq, nPadded, forces, nClear, gc);
 }
 
 // In-place refresh of the sorted per-atom parameters from the user-order values (parameter offsets / updateParametersInContext)
@@ -100,6 +112,67 @@ void launchFinishForces(const Real* fx, const Real* fy, const Real* fz, int fs, 
     dim3 grid((nAtoms + 255) / 256), block(256);
     if (isDouble) hipLaunchKernelGGL((k_finishForces<Real, double>), grid, block, 0, s, fx, fy, fz, fs, fixed, fpx, fpy, fpz, userToSorted, nAtoms, (double*)out, accumulate);
     else hipLaunchKernelGGL((k_finishForces<Real, float>), grid, block, 0, s, fx, fy, fz, fs, fixed, fpx, fpy, fpz, userToSorted, nAtoms, (float*)out, accumulate);
+}
+
+// The step's total force of every atom added to the bound context's force buffer (snb_bind_context): 64-bit fixed point, 2^32 per
+// kJ/mol/nm, long long [3][stride] in CONTEXT order.  One thread per user atom, one writer per entry.  SNB_MIXED: the direct-space part is
+// already fixed point in the accumulators and is added as an integer; the reciprocal part is truncated on its own.
+template <typename Real>
+__global__ void k_finishForcesCtx(const Real* __restrict__ fx, const Real* __restrict__ fy, const Real* __restrict__ fz, int fs, int fixed,
+                                  const Real* __restrict__ fpx, const Real* __restrict__ fpy, const Real* __restrict__ fpz,
+                                  const int* __restrict__ userToSorted, int nAtoms, long long* __restrict__ out, const int* __restrict__ userToCtx, int stride, int atomic) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= nAtoms) return;
+    const int s = userToSorted[u], slot = userToCtx[u];
+    long long x, y, z;
+    if (fixed) {
+        x = reinterpret_cast<const long long*>(fx)[(size_t)s * fs]; y = reinterpret_cast<const long long*>(fy)[(size_t)s * fs]; z = reinterpret_cast<const long long*>(fz)[(size_t)s * fs];
+        if (fpx) { x += toFixedForce64((double)fpx[s]); y += toFixedForce64((double)fpy[s]); z += toFixedForce64((double)fpz[s]); }
+    } else {
+        double dx = (double)fx[(size_t)s * fs], dy = (double)fy[(size_t)s * fs], dz = (double)fz[(size_t)s * fs];
+        if (fpx) { dx += (double)fpx[s]; dy += (double)fpy[s]; dz += (double)fpz[s]; }
+        x = toFixedForce64(dx); y = toFixedForce64(dy); z = toFixedForce64(dz);
+    }
+    ctxForceAdd(out + slot, x, atomic); ctxForceAdd(out + (size_t)stride + slot, y, atomic); ctxForceAdd(out + 2 * (size_t)stride + slot, z, atomic);
+}
+template <typename Real>
+void launchFinishForcesCtx(const Real* fx, const Real* fy, const Real* fz, int fs, int fixed, const Real* fpx, const Real* fpy, const Real* fpz,
+                           const int* userToSorted, int nAtoms, long long* out, const int* userToCtx, int stride, int atomic, hipStream_t s) {
+    if (nAtoms <= 0) return;
+    hipLaunchKernelGGL((k_finishForcesCtx<Real>), dim3((nAtoms + 255) / 256), dim3(256), 0, s, fx, fy, fz, fs, fixed, fpx, fpy, fpz, userToSorted, nAtoms, out, userToCtx, stride, atomic);
+}
+template void launchFinishForcesCtx<float>(const float*, const float*, const float*, int, int, const float*, const float*, const float*, const int*, int, long long*, const int*, int, int, hipStream_t);
+template void launchFinishForcesCtx<double>(const double*, const double*, const double*, int, int, const double*, const double*, const double*, const int*, int, long long*, const int*, int, int, hipStream_t);
+
+// ---- context binding: map upkeep and the rebuild-time user-order copy of the positions ----
+__global__ void k_ctxFill(int* __restrict__ a, int n, int value) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = value;
+}
+void launchCtxFill(int* a, int n, int value, hipStream_t s) { if (n > 0) hipLaunchKernelGGL(k_ctxFill, dim3((n + 255) / 256), dim3(256), 0, s, a, n, value); }
+// userToCtx[atomIndex[slot]] = slot.  Nothing is read or written through an index outside [0, n): an entry out of range is skipped, and
+// every userToCtx entry that is written holds a slot below n.  With `bad` (the bind's check; userToCtx pre-filled with -1) out-of-range and
+// repeated entries are counted: atomIndex is a permutation exactly when none is.
+__global__ void k_ctxInvert(const int* __restrict__ atomIndex, int n, int* __restrict__ userToCtx, int* __restrict__ bad) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int u = atomIndex[slot];
+    if (u < 0 || u >= n) { if (bad) atomicAdd(bad, 1); return; }
+    if (bad) { if (atomicExch(&userToCtx[u], slot) != -1) atomicAdd(bad, 1); }
+    else userToCtx[u] = slot;
+}
+void launchCtxInvert(const int* atomIndex, int n, int* userToCtx, int* bad, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_ctxInvert, dim3((n + 255) / 256), dim3(256), 0, s, atomIndex, n, userToCtx, bad);
+}
+template <typename T4>
+__global__ void k_ctxStagePositions(const T4* __restrict__ posq, const int* __restrict__ userToCtx, int n, T4* __restrict__ stage) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < n) stage[u] = posq[userToCtx[u]];
+}
+void launchCtxStagePositions(const void* posq, int isDouble, const int* userToCtx, int n, void* stage, hipStream_t s) {
+    if (n <= 0) return;
+    if (isDouble) hipLaunchKernelGGL((k_ctxStagePositions<double4>), dim3((n + 255) / 256), dim3(256), 0, s, (const double4*)posq, userToCtx, n, (double4*)stage);
+    else hipLaunchKernelGGL((k_ctxStagePositions<float4>), dim3((n + 255) / 256), dim3(256), 0, s, (const float4*)posq, userToCtx, n, (float4*)stage);
 }
 
 // ---- effective parameters on the device (the reference: nonbondedParameters.cc computeParameters :4-137, computePlasmaCorrection :139-179) ----
@@ -248,8 +321,21 @@ __global__ void k_finishSliceEnergies(const double* __restrict__ parts, double* 
     acc += sliceFinishClosedForm(f, i);
     out[i] = acc;
 }
-void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_finishSliceEnergies, dim3((n + 63) / 64), dim3(64), 0, s, parts, out, n, f);
+// Bound context: ONE work-group finishes every entry, then its first wave adds the lambda-weighted total and the raw values to the
+// context's accumulators (deliverEnergies)
+__global__ void __launch_bounds__(256) k_finishSliceEnergiesCtx(const double* __restrict__ parts, double* __restrict__ out, int n, SliceFinish f, EnergyOut e) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double acc = 0;
+        for (int part = 0; part < SNB_SLICE_E_PARTS; part++) acc += parts[(size_t)part * n + i];
+        out[i] = acc + sliceFinishClosedForm(f, i);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) deliverEnergies(e, out, n, threadIdx.x);
+}
+void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, const EnergyOut& e, hipStream_t s) {
+    if (n <= 0) return;
+    if (e.energy || e.deriv) hipLaunchKernelGGL(k_finishSliceEnergiesCtx, dim3(1), dim3(256), 0, s, parts, out, n, f, e);
+    else hipLaunchKernelGGL(k_finishSliceEnergies, dim3((n + 63) / 64), dim3(64), 0, s, parts, out, n, f);
 }
 
 // Zero fill as a KERNEL.  hipMemsetAsync captured into a hipGraph is a memset node, and a replayed memset node went wrong in round 4:

@@ -2085,7 +2085,9 @@ template <typename Real> __global__ __launch_bounds__(256) void k_interpolate(co
 // cost ~80 us per held grid at 300k atoms.
 // (occupancy note: ~100 VGPRs => one 1024-thread work-group per CU, 400 bricks = two rounds of ~20 us on c3; forcing 64 VGPRs spills
 // and measures 71 us, 512-thread groups 56 us, z slabs 70 us -- this shape, 52 us, is the best of those)
-template <typename Real, int NT> __global__ __launch_bounds__(NT) void k_interpolateBricks(const PmeParams<Real> p, const int zSlabs) {
+// CTX: the fused finish delivers into a bound context's fixed-point buffer (snb_bind_context); an instantiation of its own, so that the
+// user-order kernels carry none of its registers
+template <typename Real, int NT, bool CTX> __global__ __launch_bounds__(NT) void k_interpolateBricks(const PmeParams<Real> p, const int zSlabs) {
     SNB_TRACE_START(p.stepTrace, 11);
     extern __shared__ __align__(16) unsigned char s_brick_raw[];
     constexpr int HALO_LO = 1, EXTRA = 6;
@@ -2113,6 +2115,10 @@ template <typename Real, int NT> __global__ __launch_bounds__(NT) void k_interpo
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
             if (lane == 0) p.finOut[i] = acc + sliceFinishClosedForm(p.fin, i);
+        }
+        if (p.finE.energy != nullptr || p.finE.deriv != nullptr) {      // bound context: the total and the raw values into its accumulators (uniform over the work-group)
+            __syncthreads();
+            if (tid < 64) deliverEnergies(p.finE, p.finOut, p.finN, tid);
         }
     }
     Real* brick = reinterpret_cast<Real*>(s_brick_raw);
@@ -2203,10 +2209,27 @@ template <typename Real, int NT> __global__ __launch_bounds__(NT) void k_interpo
                     const int a = s_begin[r] + (v - s_pref[r]);
                     const int si = p.atomSubset[a];
                     const Real q = si >= 0 ? pmeCharge(p, a) : Real(0);
+                    // bound context, read-modify-write delivery: the atom's three entries of the fixed-point buffer lie scattered in context order (three
+                    // 64-byte sectors); a charged atom fetches them before its stencil arithmetic and adds to them after it, so that their latency
+                    // is not the tail of every wave (this work-group is the only writer of the entries in this step)
+                    long long* ctxO = nullptr; long long c0 = 0, c1 = 0, c2 = 0;
                     // the step's user-order force of this atom (fused k_finishForces): direct-space accumulator + reciprocal force
                     auto deliver = [&](Real rx_, Real ry_, Real rz_) {
                         const int u = p.sortedToUser[a];
                         if (u < 0) return;
+                        if constexpr (CTX) {      // bound context: fixed point, context order, added to (misc.hip k_finishForcesCtx)
+                            long long X, Y, Z;
+                            if (p.dfixed) {
+                                X = reinterpret_cast<const long long*>(p.dfx)[(size_t)a * p.dfs] + toFixedForce64((double)rx_); Y = reinterpret_cast<const long long*>(p.dfy)[(size_t)a * p.dfs] + toFixedForce64((double)ry_);
+                                Z = reinterpret_cast<const long long*>(p.dfz)[(size_t)a * p.dfs] + toFixedForce64((double)rz_);
+                            } else {
+                                X = toFixedForce64((double)p.dfx[(size_t)a * p.dfs] + (double)rx_); Y = toFixedForce64((double)p.dfy[(size_t)a * p.dfs] + (double)ry_); Z = toFixedForce64((double)p.dfz[(size_t)a * p.dfs] + (double)rz_);
+                            }
+                            if (ctxO) { ctxO[0] = c0 + X; ctxO[(size_t)p.ctxStride] = c1 + Y; ctxO[2 * (size_t)p.ctxStride] = c2 + Z; return; }      // (entries fetched ahead, below)
+                            long long* o = reinterpret_cast<long long*>(p.outForces) + p.userToCtx[u];
+                            ctxForceAdd(o, X, p.ctxAtomic); ctxForceAdd(o + (size_t)p.ctxStride, Y, p.ctxAtomic); ctxForceAdd(o + 2 * (size_t)p.ctxStride, Z, p.ctxAtomic);
+                            return;
+                        } else {
                         if (p.dfixed) {      // SNB_MIXED: 64-bit fixed-point accumulators, summed with the reciprocal part in double
                             const double k = 1.0 / 4294967296.0;
                             const double X = (double)reinterpret_cast<const long long*>(p.dfx)[(size_t)a * p.dfs] * k + (double)rx_, Y = (double)reinterpret_cast<const long long*>(p.dfy)[(size_t)a * p.dfs] * k + (double)ry_,
@@ -2228,6 +2251,7 @@ template <typename Real, int NT> __global__ __launch_bounds__(NT) void k_interpo
                             float* o = reinterpret_cast<float*>(p.outForces) + 3 * (size_t)u;
                             if (p.outAccumulate) { o[0] += (float)X; o[1] += (float)Y; o[2] += (float)Z; } else { o[0] = (float)X; o[1] = (float)Y; o[2] = (float)Z; }
                         }
+                        }
                     };
                     if (q == Real(0)) {                        // padding slots inside a run, uncharged atoms
                         if (p.outForces && si >= 0 && (zSlabs == 1 || zs == 0)) deliver(p.fpx[a], p.fpy[a], p.fpz[a]);
@@ -2239,6 +2263,10 @@ template <typename Real, int NT> __global__ __launch_bounds__(NT) void k_interpo
                     int idx[3]; Real fr[3];
                     gridCoord<Real>(p.recip, p.recipLo, pos.x, pos.y, pos.z, p.d.nx, p.d.ny, nz, idx, fr);
                     if (idx[2] < z0 || idx[2] >= z0 + sz) continue;       // another slab's atom
+                    if constexpr (CTX) if (p.outForces && !p.ctxAtomic) {
+                        const int u = p.sortedToUser[a];
+                        if (u >= 0) { ctxO = reinterpret_cast<long long*>(p.outForces) + p.userToCtx[u]; c0 = ctxO[0]; c1 = ctxO[(size_t)p.ctxStride]; c2 = ctxO[2 * (size_t)p.ctxStride]; }
+                    }
                     int rx = idx[0] - x0; if (rx > p.d.nx / 2) rx -= p.d.nx; else if (rx < -(p.d.nx / 2)) rx += p.d.nx;
                     int ry = idx[1] - y0; if (ry > p.d.ny / 2) ry -= p.d.ny; else if (ry < -(p.d.ny / 2)) ry += p.d.ny;
                     Real tx[5], ty[5], tz[5], dx[5], dy[5], dz[5];
@@ -2329,12 +2357,21 @@ template <typename Real> static bool launchInterpolateBricks(const PmeParams<Rea
             // with more bricks than CUs the second round of 1024-thread groups runs half empty
             const int ntEnv = switches().interpThreads;
             const bool narrow = ntEnv ? ntEnv == 512 : (nblocks > 256 && lds <= 76 * 1024);
-            if (narrow) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 512>), dim3(nblocks), dim3(512), lds, s, p, zSlabs);
+            if (!p.outForces) p.userToCtx = nullptr;
+            if (p.userToCtx) {      // bound context
+                if (narrow) {
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 512, true>), dim3(nblocks), dim3(512), lds, s, p, zSlabs);
+                } else {
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 1024, true>), dim3(nblocks), dim3(1024), lds, s, p, zSlabs);
+                }
+            } else if (narrow) {
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 512, false>), dim3(nblocks), dim3(512), lds, s, p, zSlabs);
             } else {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 1024>), dim3(nblocks), dim3(1024), lds, s, p, zSlabs);
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 1024, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 1024, false>), dim3(nblocks), dim3(1024), lds, s, p, zSlabs);
             }
             return p.outForces != nullptr;
         }

@@ -136,6 +136,44 @@ extern thread_local KernelStamps* g_stamps;
         if (ks_ && slot_ >= 0 && slot_ < 16 && ks_->start[slot_] && !ks_->used[slot_]) { ks_->used[slot_] = true; hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, ks_->start[slot_], ks_->stop[slot_], 0, __VA_ARGS__); } \
         else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__); } while (0)
 
+// ---- context binding (snb_bind_context): delivery into the caller's context-order buffers ----
+// force -> 64-bit fixed point, 2^32 per kJ/mol/nm, truncated as the reference's realToFixedPoint, saturating
+__device__ inline long long toFixedForce64(double v) {
+    v *= 4294967296.0;
+    v = fmin(fmax(v, -9223372036854774784.0), 9223372036854774784.0);      // (the largest doubles inside the 64-bit range; a NaN becomes the lower bound)
+    return (long long)v;
+}
+// one entry of the bound force buffer: exactly one writer per step; plain read-modify-write, or a 64-bit atomic without return (SNB_CTX_ATOMIC_ADD)
+__device__ inline void ctxForceAdd(long long* entry, long long v, int atomic) {
+    if (atomic) __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(entry), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *entry += v;
+}
+// Where the finished slice energies of a bound step go: total = sum_i lambda[i] * E[i] (double) added to the energy accumulator, the raw
+// E[i] added to deriv[slot[i]] for slot[i] >= 0 (entries may share a slot).  All null: nothing to deliver.
+struct EnergyOut {
+    const double* lambdas;    // [2 S] as given to snb_set_lambdas (double)
+    void* energy;             // scalar accumulator or null
+    void* deriv;              // accumulator array or null
+    const int* derivSlot;     // [2 S]
+    const int* need;          // [S] derivative-only steps: only the slices flagged here carry an energy; null: all
+    int isDouble;
+};
+// run by ONE wave once every out[i] is complete and visible to it
+__device__ inline void deliverEnergies(const EnergyOut& e, const double* out, int n, int lane) {
+    if (e.energy) {
+        double t = 0;
+        for (int i = lane; i < n; i += 64) t += e.lambdas[i] * out[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        if (lane == 0) { if (e.isDouble) *reinterpret_cast<double*>(e.energy) += t; else *reinterpret_cast<float*>(e.energy) += (float)t; }
+    }
+    if (e.deriv) for (int i = lane; i < n; i += 64) {
+        const int slot = e.derivSlot[i];
+        if (slot < 0 || (e.need && !e.need[i >> 1])) continue;
+        if (e.isDouble) atomicAdd(reinterpret_cast<double*>(e.deriv) + slot, out[i]); else atomicAdd(reinterpret_cast<float*>(e.deriv) + slot, (float)out[i]);
+    }
+}
+
 struct SliceFinish {
     const double* sums;       // [3 nsub] per-subset sum q, sum q^2, sum c6^2 (k_paramSums), or null
     const double* dispCoef;   // [S] dispersion-correction coefficients, or null
@@ -207,6 +245,8 @@ template <typename Real> struct PmeParams {
     // brick interpolation of the step's LAST mesh, unsharded: the atom's thread also writes the step's user-order force,
     // direct-space accumulator + reciprocal force, into the caller's buffer (what k_finishForces does as a launch of its own)
     void* outForces; int outIsDouble, outAccumulate;      // [N][3] in the caller's type, or null
+    const int* userToCtx; int ctxStride, ctxAtomic;      // non-null: outForces is the bound context's fixed-point buffer, long long [3][ctxStride] in context order, added to (snb_bind_context)
+    EnergyOut finE;                                      // ... and where the fused energy finish delivers the step's energies
     const double* finParts; double* finOut; int finN; SliceFinish fin;      // finOut != null: one work-group of the interpolation also sums the slice-energy partitions (the fused k_finishSliceEnergies)
     const Real* dfx; const Real* dfy; const Real* dfz; int dfs, dfixed;   // direct-space accumulators (component bases, atom stride, 64-bit fixed point)
     const int* sortedToUser;
@@ -336,6 +376,7 @@ template <typename Real> struct GatherCells {
     int* zeroInts; int nZeroInts;     // small per-step counters reset by this pass (the spreader's stray-atom counts)
     long long* stepTrace;             // SNB_STEP_TRACE
     int* zeroInts2; int nZeroInts2;   // ... and the work counter + CU table of an overlapped step's pair kernel
+    const int* userToCtx;             // bound context (snb_bind_context): the positions are [..][4] records in context order, atom u in record userToCtx[u]; null: user order
 };
 
 template <typename Real> void launchGatherPositions(const void* userPos, int isDouble, int stride4, const int* sortedToUser, const Real* imageOffset,
@@ -344,9 +385,17 @@ template <typename Real> void launchRefreshParams(const int* sortedToUser, const
                                                   typename Vec<Real>::T2* sigeps, int nPadded, hipStream_t s);
 template <typename Real> void launchFinishForces(const Real* fx, const Real* fy, const Real* fz, int fs, int fixed, const Real* fpx, const Real* fpy, const Real* fpz,
                                                  const int* userToSorted, int nAtoms, void* out, int isDouble, int accumulate, hipStream_t s);
+// the same into a bound context's fixed-point buffer (long long [3][stride], context order, added to)
+template <typename Real> void launchFinishForcesCtx(const Real* fx, const Real* fy, const Real* fz, int fs, int fixed, const Real* fpx, const Real* fpy, const Real* fpz,
+                                                    const int* userToSorted, int nAtoms, long long* out, const int* userToCtx, int stride, int atomic, hipStream_t s);
+// context binding, map upkeep (misc.hip): userToCtx[atomIndex[slot]] = slot for every in-range entry; bad (or null): counts out-of-range and repeated entries
+void launchCtxInvert(const int* atomIndex, int n, int* userToCtx, int* bad, hipStream_t s);
+void launchCtxFill(int* a, int n, int value, hipStream_t s);
+// rebuild-time user-order copy of the bound positions: stage[u] = posq[userToCtx[u]] ([N][4] records of the context's type)
+void launchCtxStagePositions(const void* posq, int isDouble, const int* userToCtx, int n, void* stage, hipStream_t s);
 
 // closed-form terms of the raw slice energies (k_finishSliceEnergies); a null pointer / zero factor switches a term off
-void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, hipStream_t s);
+void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, const EnergyOut& e, hipStream_t s);
 #define SNB_PARAM_SUM_ROWS 256      // work-groups of k_paramSums, each leaving one row of partial sums
 template <typename Real>
 void launchParticleParams(int n, int nsub, const double* base, const int* offStart, const int* offGlobal, const double* offDelta, const double* globals,

@@ -55,6 +55,7 @@ struct Switches {
     bool noSortGraph = flag("SNB_NO_SORT_GRAPH");      // test switch: phase A of the rebuild as plain launches instead of a replayed graph (0.98 vs 0.68 ms per rebuild on c3)
     bool noFusedFinish = flag("SNB_NO_FUSED_FINISH");      // test switch: k_finishForces as a kernel of its own
     bool noFusedEnergyFinish = flag("SNB_NO_FUSED_ENERGY_FINISH");      // test switch: k_finishSliceEnergies as a kernel of its own
+    bool ctxAtomicAdd = flag("SNB_CTX_ATOMIC_ADD");      // measurement aid: a bound context's force buffer (snb_bind_context) is added to with 64-bit atomics instead of plain read-modify-write
     bool concurrentPme = intOr("SNB_CONCURRENT_PME", 0) != 0;      // forces-only graph steps fork the PME chain; measured on c3: serial 0.80 ms/step, forked 0.87 (default priority) / 1.32 (high or low priority)
     bool noKernelStamps = flag("SNB_NO_KERNEL_STAMPS");      // measurement aid: only the pair-kernel / pipeline timers
     bool noPinnedRing = flag("SNB_NO_PINNED_RING");      // test switch: the copy straight from the caller's array (synchronised)
