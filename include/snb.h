@@ -248,6 +248,48 @@ snb_status snb_bind_context(snb_handle h, const snb_context_binding* b);
  * snapshot of the positions). */
 snb_status snb_context_order_changed(snb_handle h);
 
+/* -- frame batches ----------------------------------------------------------------------------- */
+/* The slice energies of F stored frames in one call: the loop of MBAR / reweighting over a trajectory (E(lambda) = sum_s lambda_s E_s, so one
+ * evaluation of a frame gives its energy at every lambda state).  Row f of slice_energies is what snb_set_box (boxes[f]), snb_set_positions
+ * (frame f), an energy-only snb_execute (include_forces = 0, include_energy = mode, energy = NULL) and snb_get_slice_energies give, to the
+ * accuracy of the precision mode (the list built for a frame orders the sums differently) -- without a host synchronisation per frame: while
+ * the energy-only step of frame f runs, the list of frame f + 1 is built beside it on an internal stream, straight from that frame's
+ * positions; host frames are uploaded through pinned staging buffers on a copy stream ahead of their build.  A frame is built in line instead
+ * when its box differs from its predecessor's, when it is the first of the batch, during the first two rebuilds of an engine, after a
+ * discarded side build, and wherever lists are built on the host (NoCutoff, fewer than 64 atoms, tiny cells) or the system is not periodic.
+ * Host output (out_is_device == 0): returns with the results written, after exactly one synchronisation, at the end.  Device output: returns
+ * once the last frame is enqueued; the results are complete in stream order on snb_config.stream.
+ * Everything is checked before anything is enqueued: a failed call leaves no work behind and no state changed.  n_frames == 0: SNB_OK, no
+ * work.  Negative count, NULL positions / slice_energies, another mode, states with mode 2: SNB_ERR_INVALID_ARGUMENT.  A box that is not in
+ * reduced form: SNB_ERR_INVALID_ARGUMENT; one smaller than twice the cutoff: SNB_ERR_BOX_TOO_SMALL; Ewald with a non-rectangular box:
+ * SNB_ERR_UNSUPPORTED -- each with the frame index in snb_last_error.
+ * Afterwards the engine is what it was: the caller's positions, the box, the lambdas and the energy-slice mask are in place, snb_get_forces
+ * returns the forces of the last forces step, the buffer of snb_set_force_output is untouched, no step graph was captured or updated; the
+ * next snb_execute rebuilds its list (the lists in memory belong to the last frame) and refreshes its graph in place, as after any rebuild.
+ * The engine's own slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) holds the last frame.  Frame steps count in
+ * snb_stats.n_rebuilds and are never timed steps.
+ * Out of scope: while a context is bound (snb_bind_context) the call returns SNB_ERR_STATE -- a binding takes its positions from posq -- and
+ * on sharded engines (shard_count > 1) SNB_ERR_UNSUPPORTED -- their energy-only steps run the forces kernels. */
+typedef struct {
+    int32_t        n_frames;
+    const void*    positions;        /* [F][N][3], or [F][N][4] when stride4 != 0; USER atom order; float or double by is_double */
+    int32_t        is_device;        /* != 0: device pointer on the engine's device, valid until the engine's stream has passed the batch */
+    int32_t        is_double;
+    int32_t        stride4;
+    const double*  boxes;            /* HOST [F][9], reduced form, or NULL: the engine's current box for every frame */
+    int32_t        mode;             /* 1: every slice; 2: the slices of snb_set_energy_slices (other entries unspecified) */
+    int32_t        include_direct, include_reciprocal;
+    double*        slice_energies;   /* [F][S][2] raw (Coulomb, vdW), complete as after an energy-only snb_execute: pair, reciprocal, self, background, dispersion correction */
+    int32_t        out_is_device;
+    int32_t        n_states;         /* optional: K lambda states, 0 = none */
+    const double*  state_lambdas;    /* HOST [K][S][2] */
+    double*        state_energies;   /* [F][K] = sum_s sum_t lambda_k[s][t] E[f][s][t], summed in double on the device; same residence as slice_energies; mode 1 only */
+} snb_frame_batch;
+snb_status snb_evaluate_frames(snb_handle h, const snb_frame_batch* b);
+
+typedef struct { int64_t n_batches, n_frames, n_built_beside, n_built_in_line, n_side_discarded; double last_batch_ms; } snb_frame_stats;
+snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out);   /* cumulative; last_batch_ms = host wall time of the last call that ended in a synchronise, else 0 */
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

@@ -19,7 +19,7 @@ SYMBOLS = [
     "snb_set_dispersion_coefficients", "snb_compute_dispersion_coefficients", "snb_set_box", "snb_set_positions",
     "snb_rebuild_neighbors", "snb_execute", "snb_get_forces", "snb_set_force_output", "snb_set_shard_blocks", "snb_get_slice_energies", "snb_slice_energies_device", "snb_synchronize",
     "snb_get_pme_parameters", "snb_get_ljpme_parameters", "snb_get_stats", "snb_reset_timers", "snb_set_timing_interval", "snb_legal_grid_size", "snb_abi_version",
-    "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed",
+    "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed", "snb_evaluate_frames", "snb_get_frame_stats",
 ]
 
 SNB_OK, SNB_ERR_INVALID_ARGUMENT, SNB_ERR_HIP, SNB_ERR_BOX_TOO_SMALL, SNB_ERR_NOT_PME, SNB_ERR_STATE, SNB_ERR_UNSUPPORTED = range(7)
@@ -53,6 +53,23 @@ class SnbContextBinding(ctypes.Structure):
         ("posq", ctypes.c_void_p), ("atom_index", ctypes.c_void_p), ("is_double", ctypes.c_int32), ("padded_n", ctypes.c_int32),
         ("force_buffer", ctypes.c_void_p), ("energy_buffer", ctypes.c_void_p), ("deriv_buffer", ctypes.c_void_p),
         ("deriv_slot", ctypes.POINTER(ctypes.c_int32)), ("energy_is_double", ctypes.c_int32),
+    ]
+
+
+class SnbFrameBatch(ctypes.Structure):
+    """snb_frame_batch: F stored frames for snb_evaluate_frames (include/snb.h)."""
+    _fields_ = [
+        ("n_frames", ctypes.c_int32), ("positions", ctypes.c_void_p), ("is_device", ctypes.c_int32), ("is_double", ctypes.c_int32),
+        ("stride4", ctypes.c_int32), ("boxes", ctypes.POINTER(ctypes.c_double)), ("mode", ctypes.c_int32), ("include_direct", ctypes.c_int32),
+        ("include_reciprocal", ctypes.c_int32), ("slice_energies", ctypes.c_void_p), ("out_is_device", ctypes.c_int32), ("n_states", ctypes.c_int32),
+        ("state_lambdas", ctypes.POINTER(ctypes.c_double)), ("state_energies", ctypes.c_void_p),
+    ]
+
+
+class SnbFrameStats(ctypes.Structure):
+    _fields_ = [
+        ("n_batches", ctypes.c_int64), ("n_frames", ctypes.c_int64), ("n_built_beside", ctypes.c_int64), ("n_built_in_line", ctypes.c_int64),
+        ("n_side_discarded", ctypes.c_int64), ("last_batch_ms", ctypes.c_double),
     ]
 
 
@@ -112,6 +129,8 @@ def lib():
     L.snb_legal_grid_size.argtypes = [i32]; L.snb_legal_grid_size.restype = i32
     L.snb_abi_version.restype = i32
     L.snb_test_fft3d.argtypes = [i32, i32, i32, i32, i32, i32, dp, dp, dp]
+    L.snb_evaluate_frames.argtypes = [vp, ctypes.POINTER(SnbFrameBatch)]
+    L.snb_get_frame_stats.argtypes = [vp, ctypes.POINTER(SnbFrameStats)]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError if the header and the library ever diverge
     _lib = L

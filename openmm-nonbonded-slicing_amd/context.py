@@ -319,6 +319,68 @@ class HipCalcSlicedNonbondedForceKernel:
             sl[mask == 0] = np.nan
         return sl
 
+    def computeSliceEnergiesForFrames(self, context, positions=None, boxes=None, slices=None, lambdaStates=None, positionsDevicePointer=None, numFrames=None):
+        """Raw per-slice energies [F][S][2] of F stored frames in one call (include/snb.h, snb_evaluate_frames): the loop of an MBAR or
+        reweighting pass over a trajectory, pipelined inside the engine -- the list of the next frame is built beside the step of this one.
+        positions: NumPy [F][N][3], float32 or float64 (host).  Frames already on the device: positionsDevicePointer=(address, isDouble) of
+        a contiguous [F][N][3] array on the engine's device, with numFrames.  boxes: [F][3][3] (or [F][9]) reduced box vectors per frame;
+        None: the context's box for every frame.  slices: as in computeSliceEnergies -- only those are evaluated, the other rows are NaN.
+        lambdaStates: [K][S][2]; then the result is (sliceEnergies, stateEnergies[F][K]), stateEnergies[f][k] = sum lambdaStates[k] *
+        sliceEnergies[f], summed on the device (every slice must be evaluated: not with slices).  Parameters and lambdas are pushed from the
+        context first; the context's own positions, the forces of the last forces step and the derivative mask stay as they are."""
+        self._push_parameters(context.getParameters())
+        box = np.ascontiguousarray(context.getPeriodicBoxVectors(), dtype=np.float64).reshape(9)
+        self._check(self._lib.snb_set_box(self._h, _dp(box)))
+        S = self.numSlices
+        b = _capi.SnbFrameBatch()
+        if positionsDevicePointer is not None:
+            if positions is not None or numFrames is None:
+                raise OpenMMException("computeSliceEnergiesForFrames: positionsDevicePointer goes with numFrames and without positions")
+            ptr, isDouble = positionsDevicePointer
+            F = int(numFrames)
+            b.positions = ctypes.c_void_p(int(ptr)); b.is_device = 1; b.is_double = int(bool(isDouble))
+        else:
+            pos = np.asarray(positions)
+            if pos.dtype != np.float32:
+                pos = pos.astype(np.float64, copy=False)
+            pos = np.ascontiguousarray(pos)
+            if pos.ndim != 3 or pos.shape[1:] != (self.numParticles, 3):
+                raise OpenMMException("computeSliceEnergiesForFrames: positions must be [F][%d][3]" % self.numParticles)
+            F = pos.shape[0]
+            b.positions = pos.ctypes.data_as(ctypes.c_void_p); b.is_device = 0; b.is_double = int(pos.dtype == np.float64)
+        b.n_frames = F; b.stride4 = 0
+        if boxes is not None:
+            bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 9))
+            if bx.shape[0] != F:
+                raise OpenMMException("computeSliceEnergiesForFrames: one box per frame")
+            b.boxes = _dp(bx)
+        b.mode = 1 if slices is None else 2
+        b.include_direct = 1; b.include_reciprocal = 1
+        out = np.zeros((F, S, 2))
+        b.slice_energies = out.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        states = None
+        if lambdaStates is not None:
+            lam = np.ascontiguousarray(np.asarray(lambdaStates, dtype=np.float64).reshape(-1, S, 2))
+            states = np.zeros((F, lam.shape[0]))
+            b.n_states = lam.shape[0]; b.state_lambdas = _dp(lam); b.state_energies = states.ctypes.data_as(ctypes.c_void_p)
+        if slices is None:
+            self._check(self._lib.snb_evaluate_frames(self._h, ctypes.byref(b)))
+        else:
+            mask = np.zeros(S, dtype=np.int32)
+            mask[np.asarray(list(slices), dtype=np.int64)] = 1
+            self._check(self._lib.snb_set_energy_slices(self._h, _ip(mask)))
+            try:
+                self._check(self._lib.snb_evaluate_frames(self._h, ctypes.byref(b)))
+            finally:      # (the derivative-only steps of execute() keep their own mask)
+                self._check(self._lib.snb_set_energy_slices(self._h, _ip(self._derivMask)))
+            out[:, mask == 0] = np.nan
+        return out if states is None else (out, states)
+
+    def getFrameStats(self):
+        st = _capi.SnbFrameStats()
+        self._check(self._lib.snb_get_frame_stats(self._h, ctypes.byref(st)))
+        return st
+
     # -- CalcSlicedNonbondedForceKernel::copyParametersToContext (NonbondedSlicingKernels.h:66) ------
     def copyParametersToContext(self, context, force):
         if force.getNumParticles() != self.numParticles:

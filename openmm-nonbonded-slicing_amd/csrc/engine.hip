@@ -109,6 +109,8 @@ struct EngineBase {
     virtual void resetTimers() = 0;
     virtual void setTimingInterval(int) = 0;
     virtual void getPme(double*, int32_t*, bool dispersion) = 0;
+    virtual void evaluateFrames(const snb_frame_batch*) = 0;
+    virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
 // ---- dispersion coefficients (SlicedNonbondedForceImpl.cpp:150-185, 263-354), doubles throughout ----
@@ -273,7 +275,18 @@ public:
     } shadow;
     hipStream_t streamBuild = nullptr; hipEvent_t evSnap = nullptr, evBuilt = nullptr, evFlagsReset = nullptr; bool flagsResetPending = false; DevBuf<unsigned char> posSnap;
     bool sortGraphSuspect = false;      // see gpuRebuild
+    // Frame batches (snb_evaluate_frames, evaluateFrames below): the list of frame f + 1 is built on streamBuild into the shadow set, straight
+    // from that frame's positions, while the energy-only step of frame f runs on the step stream.  Host frames arrive through two pinned
+    // staging buffers on a copy stream, ahead of their build.  evFrameStep[f & 1] follows the step of frame f: whatever rewrites something
+    // that step read (the shadow set, a staging slot) waits for it on its own stream -- the host never drains the step stream between frames.
+    snb_frame_stats fstats;
+    double* frameRow = nullptr;      // the row of the caller's table the step's finish kernel also writes (null outside a batch)
+    bool plainSort = false;      // frame builds issue phase A as plain launches: every frame is another position pointer, i.e. another graph key
+    hipStream_t streamCopy = nullptr; hipEvent_t evFrameStep[2] = {nullptr, nullptr}, evFrameUp[2] = {nullptr, nullptr}, evBatchStart = nullptr; bool frameUpPending[2] = {false, false};
+    void* framePinned[2] = {nullptr, nullptr}; size_t framePinnedCap[2] = {0, 0}; DevBuf<unsigned char> frameDev[2];
+    DevBuf<double> frameRows, frameStates, dStateLambdas;
     bool sideBuilding = false, sidePending = false; int sideSeq = 0; long long sideBuilds = 0, sideDiscarded = 0;
+    int lastPadCount = 0;      // the exact padded count of the last accepted build (what a frame batch sizes its own prediction from)
     int npadPredict = 0; long long padMispredictions = 0;      // > 0: size of the padded arrays the next GPU rebuild assumes (gpuRebuild); how often that was too small
     int Npad = 0, numBlocks = 0; int64_t numTiles = 0, numMaskTiles = 0, shardTiles = 0; bool wrapMode = false;
     std::vector<int> sortedToUser, userToSorted;
@@ -439,7 +452,7 @@ public:
 
     Engine(const snb_config& c) {
         cfg = c; N = c.n_atoms; nsub = c.n_subsets; S = nsub * (nsub + 1) / 2;
-        std::memset(&stats, 0, sizeof(stats));
+        std::memset(&stats, 0, sizeof(stats)); std::memset(&fstats, 0, sizeof(fstats));
         HIPCHECK(hipSetDevice(c.device));
         if (c.stream) stream = (hipStream_t)c.stream; else { HIPCHECK(hipStreamCreate(&stream)); ownStream = true; }
         ring.resize(RING);
@@ -504,6 +517,9 @@ public:
         if (dPmeTrace.p) { long long h[4] = {0, 0, 0, 0}; (void)hipMemcpy(h, dPmeTrace.p, 32, hipMemcpyDeviceToHost); if (h[2] > 0) fprintf(stderr, "[snb] interpolation bricks: mean load %.2f us, mean compute %.2f us per work-group (%lld work-groups)\n", h[0] / 100.0 / h[2], h[1] / 100.0 / h[2], h[2]); }
         destroyGraphs();
         if (streamBuild) { (void)hipStreamSynchronize(streamBuild); (void)hipStreamDestroy(streamBuild); if (evSnap) (void)hipEventDestroy(evSnap); if (evBuilt) (void)hipEventDestroy(evBuilt); if (evFlagsReset) (void)hipEventDestroy(evFlagsReset); }
+        if (streamCopy) { (void)hipStreamSynchronize(streamCopy); (void)hipStreamDestroy(streamCopy); }
+        for (int k = 0; k < 2; k++) { if (evFrameStep[k]) (void)hipEventDestroy(evFrameStep[k]); if (evFrameUp[k]) (void)hipEventDestroy(evFrameUp[k]); if (framePinned[k]) (void)hipHostFree(framePinned[k]); }
+        if (evBatchStart) (void)hipEventDestroy(evBatchStart);
         for (auto& g : sortGraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
         sortGraphs.clear();
         for (auto& r : ring) { for (int k = 0; k < 5; k++) (void)hipEventDestroy(r.e[k]); for (int k = 0; k < 16; k++) { (void)hipEventDestroy(r.ks.start[k]); (void)hipEventDestroy(r.ks.stop[k]); } }
@@ -1143,6 +1159,7 @@ public:
         shardTiles = numTiles;      // the builder only emitted the blocks this engine owns
         // next rebuild's array size: this count + 0.4 % + 8 blocks (c3: 300 k atoms move its count by a few blocks between rebuilds); never shrinking,
         // so that the buffers -- and the step graph's arguments -- stay where they are
+        lastPadCount = h[7];
         npadPredict = std::max(npadPredict, ((int)(h[7] * 1.004) + 256 + 31) / 32 * 32);
         if (sw.nbPredictShort > 0) npadPredict = std::max(32, h[7] - 32 * sw.nbPredictShort);
         stats.n_rebuilds++;
@@ -1166,25 +1183,33 @@ public:
         return sw.sideRebuild && !sidePending && gpuBuilt && cfg.rebuild_interval > sw.sideLead + 1 && cfg.neighbor_padding > 0 && isPeriodic() && !cfg.host_neighbor_build && !cfg.disable_graph
                && !needRebuild && !paramsDirty && !staticDirty && !valuesDirty && !excValuesDirty && npadPredict > 0 && npadPredict == Npad && hNbPub && dNbPub && devUserPos;
     }
-    // Copies the positions aside (in stream order: the positions of the step just enqueued) and enqueues the whole build on streamBuild, into
-    // the shadow buffers.  Nothing the steps use is touched; the host does not wait.
-    void startSideBuild() {
-        if (!streamBuild) {
-            int lo = 0, hi = 0;
-            HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            // (normal priority: at the lowest the build crawls and the steps end up waiting for it, at the highest its kernels push the tile kernel aside)
-            HIPCHECK(hipStreamCreateWithPriority(&streamBuild, hipStreamNonBlocking, sw.sidePrioHigh ? hi : (sw.sidePrioLow ? lo : (lo + hi) / 2)));
-            HIPCHECK(hipEventCreateWithFlags(&evSnap, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evBuilt, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evFlagsReset, hipEventDisableTiming));
+    void ensureBuildStream() {
+        if (streamBuild) return;
+        int lo = 0, hi = 0;
+        HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        // (normal priority: at the lowest the build crawls and the steps end up waiting for it, at the highest its kernels push the tile kernel aside)
+        HIPCHECK(hipStreamCreateWithPriority(&streamBuild, hipStreamNonBlocking, sw.sidePrioHigh ? hi : (sw.sidePrioLow ? lo : (lo + hi) / 2)));
+        HIPCHECK(hipEventCreateWithFlags(&evSnap, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evBuilt, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evFlagsReset, hipEventDisableTiming));
+    }
+    // Enqueues the whole build on streamBuild, into the shadow buffers.  Nothing the steps use is touched; the host does not wait.
+    // src == null (MD, fixed interval): the positions are copied aside first, in stream order -- the positions of the step just enqueued -- and
+    // the build follows that copy.  src != null (frame batches): the build reads src, positions in the current format that the caller keeps
+    // valid, and the caller has already ordered streamBuild behind the last step that used the shadow set and behind the arrival of src.
+    // When the list comes into use is the caller's decision as well: it calls finishSideBuild.
+    void startSideBuild(const void* src = nullptr) {
+        ensureBuildStream();
+        if (!src) {
+            const size_t bytes = (size_t)N * (posStride4 ? 4 : 3) * (posIsDouble ? 8 : 4);
+            posSnap.resize(bytes);
+            if (ctx.on) stageCtxPositions(posSnap.p);      // (bound context: the snapshot is taken in USER order, so the build does not depend on the context's order)
+            else HIPCHECK(hipMemcpyAsync(posSnap.p, devUserPos, bytes, hipMemcpyDeviceToDevice, stream));
+            HIPCHECK(hipEventRecord(evSnap, stream));
+            HIPCHECK(hipStreamWaitEvent(streamBuild, evSnap, 0));
+            src = posSnap.p;
         }
-        const size_t bytes = (size_t)N * (posStride4 ? 4 : 3) * (posIsDouble ? 8 : 4);
-        posSnap.resize(bytes);
-        if (ctx.on) stageCtxPositions(posSnap.p);      // (bound context: the snapshot is taken in USER order, so the build does not depend on the context's order)
-        else HIPCHECK(hipMemcpyAsync(posSnap.p, devUserPos, bytes, hipMemcpyDeviceToDevice, stream));
-        HIPCHECK(hipEventRecord(evSnap, stream));
-        HIPCHECK(hipStreamWaitEvent(streamBuild, evSnap, 0));
         const hipStream_t liveStream = stream; const void* livePos = devUserPos;
         const int liveCells[2] = {colCells[0], colCells[1]};
-        swapListSets(); stream = streamBuild; devUserPos = posSnap.p; sideBuilding = true;
+        swapListSets(); stream = streamBuild; devUserPos = src; sideBuilding = true;
         bool ok = false;
         try {
             ok = gpuRebuild();
@@ -1313,7 +1338,7 @@ public:
             // is the insurance that caught nothing since: a padded count that doubles out of a replayed graph is built once more without it.)
             // (above 2^20 keys rocprim's radix sort takes its onesweep path, which clears its histogram with hipMemsetAsync -- a memset node if
             // captured: such systems issue phase A as plain launches)
-            if (!noSortGraph && !sortGraphBroken && !cfg.disable_graph && !sortGraphSuspect && N <= (1 << 20)) {
+            if (!noSortGraph && !sortGraphBroken && !cfg.disable_graph && !sortGraphSuspect && !plainSort && N <= (1 << 20)) {
                 hipGraphExec_t sortGraphExec = nullptr;
                 for (auto& g : sortGraphs) if (g.key.size() == sizeof(key) && std::memcmp(g.key.data(), &key, sizeof(key)) == 0) sortGraphExec = g.exec;
                 if (!sortGraphExec) {
@@ -1671,6 +1696,163 @@ public:
         } else if (energyOut) *energyOut = 0.0;
     }
 
+
+    // ------------------------------------------------------------------------------------------
+    // Frame batches (snb_evaluate_frames): F stored frames, one energy-only step each, rows of raw slice energies out.
+    // ------------------------------------------------------------------------------------------
+    // may the list of the NEXT frame be built beside the step of this one?  What sideBuildPossible asks of an MD rebuild, without the interval
+    bool frameSideBuildPossible() const {
+        return sw.sideRebuild && !sw.framesInLine && !sidePending && gpuBuilt && isPeriodic() && !cfg.host_neighbor_build
+               && !needRebuild && !paramsDirty && !staticDirty && !valuesDirty && !excValuesDirty && npadPredict > 0 && npadPredict == Npad && hNbPub && dNbPub;
+    }
+    void ensureFrameResources(bool hostFrames, size_t frameBytes) {
+        for (int k = 0; k < 2; k++) if (!evFrameStep[k]) HIPCHECK(hipEventCreateWithFlags(&evFrameStep[k], hipEventDisableTiming));
+        if (!evBatchStart) HIPCHECK(hipEventCreateWithFlags(&evBatchStart, hipEventDisableTiming));
+        ensureBuildStream();
+        if (!hostFrames) return;
+        if (!streamCopy) HIPCHECK(hipStreamCreateWithFlags(&streamCopy, hipStreamNonBlocking));
+        for (int k = 0; k < 2; k++) {
+            if (!evFrameUp[k]) HIPCHECK(hipEventCreateWithFlags(&evFrameUp[k], hipEventDisableTiming));
+            if (frameUpPending[k]) { HIPCHECK(hipEventSynchronize(evFrameUp[k])); frameUpPending[k] = false; }
+            if (framePinnedCap[k] < frameBytes) {
+                if (framePinned[k]) { (void)hipHostFree(framePinned[k]); framePinned[k] = nullptr; framePinnedCap[k] = 0; }
+                HIPCHECK(hipHostMalloc(&framePinned[k], std::max<size_t>(frameBytes, 4096), hipHostMallocDefault)); framePinnedCap[k] = std::max<size_t>(frameBytes, 4096);
+            }
+            frameDev[k].resize(frameBytes);
+        }
+    }
+    void evaluateFrames(const snb_frame_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        // ---- everything is checked before anything is enqueued or changed
+        if (b->n_frames < 0) { err = "snb_evaluate_frames: negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (ctx.on) { err = "snb_evaluate_frames: a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        if (cfg.shard_count > 1) { err = "snb_evaluate_frames: not available with shard_count > 1"; throw (int)SNB_ERR_UNSUPPORTED; }
+        const int F = b->n_frames;
+        if (F == 0) return;
+        if (!b->positions || !b->slice_energies) { err = "snb_evaluate_frames: positions and slice_energies must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (b->mode != 1 && b->mode != 2) { err = "snb_evaluate_frames: mode must be 1 (every slice) or 2 (the slices of snb_set_energy_slices)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const int K = b->n_states;
+        if (K < 0 || (K > 0 && (b->mode != 1 || !b->state_lambdas || !b->state_energies))) { err = "snb_evaluate_frames: lambda states need mode 1, state_lambdas and state_energies"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (!haveParticles) throw HipError{"snb_evaluate_frames: particles were not set"};
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
+        const bool frameBoxes = isPeriodic() && b->boxes != nullptr;
+        if (isPeriodic()) {
+            if (!frameBoxes && !haveBox) throw HipError{"snb_evaluate_frames: box was not set"};
+            const double minAllowed = 1.999999 * cfg.cutoff;
+            for (int f = 0; f < (frameBoxes ? F : 1); f++) {
+                const double* x = frameBoxes ? b->boxes + 9 * (size_t)f : box;
+                if (x[1] != 0 || x[2] != 0 || x[5] != 0) throw HipError{"snb_evaluate_frames: frame " + std::to_string(f) + ": box vectors must be in reduced (lower triangular) form"};
+                if (!(x[0] >= minAllowed && x[4] >= minAllowed && x[8] >= minAllowed)) { err = "snb_evaluate_frames: frame " + std::to_string(f) + ": The periodic box size has decreased to less than twice the nonbonded cutoff."; throw (int)SNB_ERR_BOX_TOO_SMALL; }
+                if (cfg.method == SNB_Ewald && recip && (x[3] != 0 || x[6] != 0 || x[7] != 0)) { err = "snb_evaluate_frames: frame " + std::to_string(f) + ": SlicedNonbondedForce: Ewald is not supported with non-rectangular boxes.  Use PME instead."; throw (int)SNB_ERR_UNSUPPORTED; }
+            }
+        }
+        if (cfg.method == SNB_Ewald && recip && (cfg.kmax[0] < 1 || cfg.kmax[1] < 1 || cfg.kmax[2] < 1)) { err = "Ewald: kmax must be given explicitly (snb_config.kmax)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        // ---- the engine's own state, put back when the batch is through
+        const void* const savedPos = devUserPos; const int savedIsDouble = posIsDouble, savedStride4 = posStride4; const bool savedHavePos = havePositions, savedHaveBox = haveBox;
+        double savedBox[9]; for (int i = 0; i < 9; i++) savedBox[i] = box[i];
+        const long long discardedBefore = sideDiscarded; const int savedPredict = npadPredict;
+        const size_t rowLen = (size_t)S * 2;
+        const bool hostFrames = b->is_device == 0, hostOut = b->out_is_device == 0;
+        const size_t frameBytes = (size_t)N * (b->stride4 ? 4 : 3) * (b->is_double ? 8 : 4);
+        auto restore = [&]() {
+            devUserPos = savedPos; posIsDouble = savedIsDouble; posStride4 = savedStride4; havePositions = savedHavePos; haveBox = savedHaveBox;
+            for (int i = 0; i < 9; i++) box[i] = savedBox[i];
+            frameRow = nullptr; plainSort = false; energySelective = false;
+            if (savedPredict > 0) npadPredict = savedPredict;      // (MD rebuilds size their arrays as they did before the batch; an engine that had no prediction yet keeps the batch's, so that the next batch pipelines from its second frame)
+            needRebuild = true;      // the lists in memory belong to the last frame
+        };
+        try {
+            if (dLambdas.p == nullptr) setLambdas(lambdas.data());
+            if (sidePending) cancelSideBuild();      // (an MD side build in flight: its list would come into use after frames it knows nothing of)
+            keepLastForces();      // before the first frame's rebuild re-sorts the atoms
+            ensureFrameResources(hostFrames, frameBytes);
+            double* rows = b->slice_energies;
+            if (hostOut) { frameRows.resize((size_t)F * rowLen); rows = frameRows.p; }
+            posIsDouble = b->is_double ? 1 : 0; posStride4 = b->stride4 ? 1 : 0; havePositions = true; plainSort = true;
+            // The batch's own padded-count prediction: unrelated frames move the count further than consecutive MD rebuilds do (MD: last count
+            // + 0.4 % + 8 blocks), so a batch sizes the arrays by the last exact count + 3 % + 32 blocks, from its first frame's build on, and
+            // keeps that size while a frame's count leaves it 8 spare blocks -- a prediction that moved with every new maximum would no longer
+            // equal the arrays' size, which costs the next frame its side build.
+            int batchPredict = 0;
+            auto widePrediction = [](int count) { return ((int)(count * 1.03) + 1024 + 31) / 32 * 32; };
+            auto predictForFrames = [&]() {      // after a build was accepted (gpuBuilt), or before the first frame
+                if (lastPadCount <= 0 || npadPredict <= 0) return;
+                if (batchPredict == 0 || lastPadCount + 256 > batchPredict) batchPredict = std::max(std::max(batchPredict, npadPredict), widePrediction(lastPadCount));
+                npadPredict = batchPredict;
+            };
+            predictForFrames();
+            long long nBeside = 0, nInLine = 0;
+            HIPCHECK(hipEventRecord(evBatchStart, stream));      // (staging slots and the shadow set may still be read by what was enqueued before the batch)
+            auto frameBox = [&](int f) { return frameBoxes ? b->boxes + 9 * (size_t)f : savedBox; };
+            auto sameBox = [&](int f, int g) { return std::memcmp(frameBox(f), frameBox(g), 9 * sizeof(double)) == 0; };
+            // the event behind the last step that read what frame g is about to overwrite (its staging slot, the shadow set): the step of frame g - 2
+            auto freeEvent = [&](int g) { return g >= 2 ? evFrameStep[g & 1] : evBatchStart; };
+            // frame g on the device: the caller's own buffer, or its staging slot, filled by the copy stream
+            auto stage = [&](int g) -> const void* {
+                const unsigned char* src = static_cast<const unsigned char*>(b->positions) + (size_t)g * frameBytes;
+                if (!hostFrames) return src;
+                const int slot = g & 1;
+                if (frameUpPending[slot]) { HIPCHECK(hipEventSynchronize(evFrameUp[slot])); frameUpPending[slot] = false; }      // (the copy of frame g - 2 out of this pinned slot: long done)
+                std::memcpy(framePinned[slot], src, frameBytes);
+                HIPCHECK(hipStreamWaitEvent(streamCopy, freeEvent(g), 0));
+                HIPCHECK(hipMemcpyAsync(frameDev[slot].p, framePinned[slot], frameBytes, hipMemcpyHostToDevice, streamCopy));
+                HIPCHECK(hipEventRecord(evFrameUp[slot], streamCopy)); frameUpPending[slot] = true;
+                return frameDev[slot].p;
+            };
+            const void* cur = stage(0);
+            if (hostFrames) HIPCHECK(hipStreamWaitEvent(stream, evFrameUp[0], 0));
+            for (int f = 0; f < F; f++) {
+                if (frameBoxes) { for (int i = 0; i < 9; i++) box[i] = frameBox(f)[i]; haveBox = true; }
+                devUserPos = cur;
+                bool beside = false;
+                if (sidePending) beside = finishSideBuild();      // (started behind the previous frame's step, from this frame's positions; spins on the build's totals only)
+                if (beside) nBeside++;
+                else {
+                    if (valuesDirty || excValuesDirty) { staticDirty = true; valuesDirty = excValuesDirty = false; }
+                    if (hostFrames) HIPCHECK(hipEventSynchronize(evFrameUp[f & 1]));      // (an in-line build may read the positions back to the host)
+                    rebuild();
+                    nInLine++;
+                }
+                if (gpuBuilt) predictForFrames();
+                stepsSinceRebuild++;
+                energySelective = b->mode == 2; ctxAddTotal = false;
+                frameRow = rows + (size_t)f * rowLen;
+                enqueueStep(true, direct, recip, nullptr, StepForces::None);      // plain launches, never stamped: no step graph is captured or updated
+                frameRow = nullptr;
+                HIPCHECK(hipEventRecord(evFrameStep[f & 1], stream));
+                if (f + 1 < F) {
+                    cur = stage(f + 1);
+                    if (sameBox(f, f + 1) && frameSideBuildPossible()) {      // (column geometry, PME brick plans and the plane table follow the box: a changed box builds in line)
+                        HIPCHECK(hipStreamWaitEvent(streamBuild, freeEvent(f + 1), 0));
+                        if (hostFrames) HIPCHECK(hipStreamWaitEvent(streamBuild, evFrameUp[(f + 1) & 1], 0));
+                        startSideBuild(cur);
+                    }
+                    if (hostFrames) HIPCHECK(hipStreamWaitEvent(stream, evFrameUp[(f + 1) & 1], 0));
+                }
+            }
+            double* states = b->state_energies;
+            if (K > 0) {
+                pinned.upload(dStateLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * rowLen), stream);
+                if (hostOut) { frameStates.resize((size_t)F * K); states = frameStates.p; }
+                launchFrameStateEnergies(rows, dStateLambdas.p, states, F, K, (int)rowLen, stream);
+            }
+            energyPending = true;      // (the engine's own buffer holds the last frame's sums)
+            fstats.n_batches++; fstats.n_frames += F; fstats.n_built_beside += nBeside; fstats.n_built_in_line += nInLine; fstats.n_side_discarded += sideDiscarded - discardedBefore; fstats.last_batch_ms = 0;
+            if (hostOut) {      // the one synchronisation of a batch with host output
+                HIPCHECK(hipMemcpyAsync(b->slice_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+                if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_energies, states, sizeof(double) * (size_t)F * K, hipMemcpyDeviceToHost, stream));
+                HIPCHECK(hipStreamSynchronize(stream));
+                fstats.last_batch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            }
+        } catch (...) {
+            if (sidePending) { try { cancelSideBuild(); } catch (...) {} }
+            restore();
+            throw;
+        }
+        restore();
+    }
+    void getFrameStats(snb_frame_stats* o) override { *o = fstats; }
+
     // SNB_OVERLAP_DEBUG: how the limited launch of the last overlapped step spread over the physical CUs (synchronises)
     void dumpOverlapTable() {
         std::vector<int> h(SNB_OVERLAP_INTS);
@@ -1882,7 +2064,7 @@ public:
         if (energy) {
             const SliceFinish f = makeSliceFinish(includeDirect, includeRecip);
             if (!(finished && energyFinished))
-            launchFinishSliceEnergies(sliceE.p, sliceTotal.p, 2 * S, f, eo, stream);
+            launchFinishSliceEnergies(sliceE.p, sliceTotal.p, 2 * S, f, eo, stream, frameRow);
         }
         if (ev) HIPCHECK(hipEventRecord(ev->e[4], stream));
     }
@@ -2137,6 +2319,11 @@ snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]
 snb_status snb_reset_timers(snb_handle h) { return guard(h, [&] { h->impl->resetTimers(); }); }
 snb_status snb_set_timing_interval(snb_handle h, int32_t n) { return guard(h, [&] { h->impl->setTimingInterval(n); }); }
 snb_status snb_get_stats(snb_handle h, snb_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getStats(out); }); }
+snb_status snb_evaluate_frames(snb_handle h, const snb_frame_batch* b) {
+    if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_frames: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
+    return guard(h, [&] { h->impl->evaluateFrames(b); });
+}
+snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 
 snb_status snb_test_fft3d(int32_t precision, int32_t device, int32_t batch, int32_t nx, int32_t ny, int32_t nz, const double* in, double* spectrum, double* roundtrip) {
     if (!in || !spectrum || !roundtrip || batch < 1) return SNB_ERR_INVALID_ARGUMENT;

@@ -313,13 +313,16 @@ template void launchExceptionParams<double>(int, const double*, const int*, cons
 // dispersion correction coef_s / V (ReferenceNonbondedSlicingKernels.cpp:244-249) -- so that an energy / derivative step needs no
 // host arithmetic and no synchronisation: the host (or the caller's own kernel, snb_slice_energies_device) reads 2 S doubles when
 // it wants them.
-__global__ void k_finishSliceEnergies(const double* __restrict__ parts, double* __restrict__ out, int n, SliceFinish f) {
+// row (frame batches, snb_evaluate_frames): the frame's row of the caller's [F][S][2] table gets the same sums in the same launch -- no copy
+// per frame; out keeps the last frame, so snb_get_slice_energies stays meaningful.  Null on every other step.
+__global__ void k_finishSliceEnergies(const double* __restrict__ parts, double* __restrict__ out, int n, SliceFinish f, double* __restrict__ row) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double acc = 0;
     for (int part = 0; part < SNB_SLICE_E_PARTS; part++) acc += parts[(size_t)part * n + i];
     acc += sliceFinishClosedForm(f, i);
     out[i] = acc;
+    if (row) row[i] = acc;
 }
 // Bound context: ONE work-group finishes every entry, then its first wave adds the lambda-weighted total and the raw values to the
 // context's accumulators (deliverEnergies)
@@ -332,10 +335,27 @@ __global__ void __launch_bounds__(256) k_finishSliceEnergiesCtx(const double* __
     __syncthreads();
     if (threadIdx.x < 64) deliverEnergies(e, out, n, threadIdx.x);
 }
-void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, const EnergyOut& e, hipStream_t s) {
+void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, const EnergyOut& e, hipStream_t s, double* row) {
     if (n <= 0) return;
-    if (e.energy || e.deriv) hipLaunchKernelGGL(k_finishSliceEnergiesCtx, dim3(1), dim3(256), 0, s, parts, out, n, f, e);
-    else hipLaunchKernelGGL(k_finishSliceEnergies, dim3((n + 63) / 64), dim3(64), 0, s, parts, out, n, f);
+    if (e.energy || e.deriv) hipLaunchKernelGGL(k_finishSliceEnergiesCtx, dim3(1), dim3(256), 0, s, parts, out, n, f, e);      // (bound engines take no frame batches: no row)
+    else hipLaunchKernelGGL(k_finishSliceEnergies, dim3((n + 63) / 64), dim3(64), 0, s, parts, out, n, f, row);
+}
+
+// Frame batches: the energies of K lambda states from the raw slice energies of F frames, E[f][k] = sum_i lambda[k][i] rows[f][i] over the
+// n = 2 S entries of a row, in double: one thread per (frame, state), one launch per batch behind the last frame's finish.
+__global__ void k_frameStateEnergies(const double* __restrict__ rows, const double* __restrict__ lambdas, double* __restrict__ out, long long nOut, int nStates, int n) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nOut) return;
+    const double* r = rows + (size_t)(t / nStates) * n;
+    const double* l = lambdas + (size_t)(t % nStates) * n;
+    double acc = 0;
+    for (int i = 0; i < n; i++) acc += l[i] * r[i];
+    out[t] = acc;
+}
+void launchFrameStateEnergies(const double* rows, const double* lambdas, double* out, int nFrames, int nStates, int n, hipStream_t s) {
+    const long long nOut = (long long)nFrames * nStates;
+    if (nOut <= 0) return;
+    hipLaunchKernelGGL(k_frameStateEnergies, dim3((unsigned)((nOut + 255) / 256)), dim3(256), 0, s, rows, lambdas, out, nOut, nStates, n);
 }
 
 // Zero fill as a KERNEL.  hipMemsetAsync captured into a hipGraph is a memset node, and a replayed memset node went wrong in round 4:

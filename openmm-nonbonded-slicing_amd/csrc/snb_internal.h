@@ -395,7 +395,10 @@ void launchCtxFill(int* a, int n, int value, hipStream_t s);
 void launchCtxStagePositions(const void* posq, int isDouble, const int* userToCtx, int n, void* stage, hipStream_t s);
 
 // closed-form terms of the raw slice energies (k_finishSliceEnergies); a null pointer / zero factor switches a term off
-void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, const EnergyOut& e, hipStream_t s);
+// row: frame batches -- also written to this row of the caller's table (null: no)
+void launchFinishSliceEnergies(const double* parts, double* out, int n, const SliceFinish& f, const EnergyOut& e, hipStream_t s, double* row = nullptr);
+// frame batches: out[f][k] = sum_i lambdas[k][i] * rows[f][i], i < n = 2 S, in double
+void launchFrameStateEnergies(const double* rows, const double* lambdas, double* out, int nFrames, int nStates, int n, hipStream_t s);
 #define SNB_PARAM_SUM_ROWS 256      // work-groups of k_paramSums, each leaving one row of partial sums
 template <typename Real>
 void launchParticleParams(int n, int nsub, const double* base, const int* offStart, const int* offGlobal, const double* offDelta, const double* globals,

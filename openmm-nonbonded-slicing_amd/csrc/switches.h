@@ -84,6 +84,7 @@ struct Switches {
     bool sideReject = flag("SNB_SIDE_REJECT");      // test switch: every side build is discarded and the rebuild repeated in line
     bool sidePrioHigh = flag("SNB_SIDE_PRIO_HIGH");      // the side-build stream at the highest priority: its kernels push the tile kernel aside (wins over _LOW; default: the middle)
     bool sidePrioLow = flag("SNB_SIDE_PRIO_LOW");      // the side-build stream at the lowest priority: the build crawls and the steps end up waiting for it
+    bool framesInLine = flag("SNB_FRAMES_IN_LINE");      // measurement aid: snb_evaluate_frames builds the list of every frame in line, none beside the previous frame's step
     // ---- diagnostics
     bool nbTrace = flag("SNB_NB_TRACE");      // per-block trace array of the tile builder
     bool pmeTrace = flag("SNB_PME_TRACE");      // trace words of the PME kernels
