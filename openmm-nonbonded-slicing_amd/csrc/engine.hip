@@ -1311,7 +1311,16 @@ public:
         for (int i = 0; i < 9; i++) p.boxm[i] = box[i];
         for (int d = 0; d < 3; d++) p.origin[d] = origin[d];
         for (int i = 0; i < 9; i++) tileCell[i] = box[i];
-        p.listCutoff = (float)R;
+        // The builder measures in float whatever the engine's precision, on coordinates held relative to the cell and shifted by up to two
+        // lattice vectors; the pair kernel then decides r < cutoff in the engine's own precision.  A pair within that float rounding of the
+        // list radius (a double engine without a skin: a pair at cutoff (1 - 1e-9)) must still be in the list, so the radius is widened by a
+        // bound on the rounding: coordinates reach 3 * span (span: the longest coordinate range of the cell), a float there is spaced
+        // 3 * span * 2^-23, and a component of a difference carries about three such roundings (stored i and j, the image shift), the block
+        // boxes two more; times sqrt(3) for the distance, plus the rounding of the squares and their sum.  1.5e-4 nm in a 40 nm cell.
+        double span = 0;
+        for (int d = 0; d < 3; d++) span = std::max(span, std::fabs(box[d]) + std::fabs(box[3 + d]) + std::fabs(box[6 + d]));
+        const double listSlack = (32.0 * span + 4.0 * R) * std::ldexp(1.0, -23);
+        p.listCutoff = (float)(R + listSlack);
         p.boxWalk = sw.nbBoxWalk ? 1 : 0;
         p.jumpDist = (float)(2.0 * std::sqrt(2.0) * std::max(box[0] / ncx, box[4] / ncy));   // neighbours along the sort path of a dense region are closer than this
         p.uSubset = dUSubset.p; p.uCharge = dUCharge.p; p.uSigEps = dUSigEps.p; p.uExclStart = exclStart.p; p.uExclList = exclList.p;
