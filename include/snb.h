@@ -290,6 +290,30 @@ snb_status snb_evaluate_frames(snb_handle h, const snb_frame_batch* b);
 typedef struct { int64_t n_batches, n_frames, n_built_beside, n_built_in_line, n_side_discarded; double last_batch_ms; } snb_frame_stats;
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out);   /* cumulative; last_batch_ms = host wall time of the last call that ended in a synchronise, else 0 */
 
+/* -- per-atom interaction energies ------------------------------------------------------------- */
+/* Where a slice's energy sits: atom_energies[i][J][t] = the raw energy (t = 0 Coulomb, 1 vdW; not scaled by the lambdas, independent of them) of
+ * atom i with ALL atoms of subset J, for every atom and every subset in one evaluation -- what one subset (and one PME mesh) per residue
+ * would cost a mesh each.  It is the energy the slice (n, J) would have with atom i alone in a new subset n; in its own subset's column the
+ * atom's self-interaction (its images, the Ewald self term) counts twice, so that
+ *     sum_{i in I} A[i][J] = E[slice(I, J)]  (I != J),        1/2 sum_{i in I} A[i][I] = E[slice(I, I)]
+ * with E the raw slice energies of an energy-only step without dispersion-correction coefficients.  Pairs inside the cutoff, the Ewald
+ * exclusion corrections and the 1-4 exceptions credit both ends; the reciprocal part is q_i psi_J(r_i) from the unmixed potentials of the
+ * subsets' meshes (LJPME: c6_i psi_J of the dispersion mesh into t = 1); the neutralising background is -2 c q_i Q_J.  The long-range
+ * dispersion correction is a per-slice constant, coef / V (snb_compute_dispersion_coefficients), and is NOT attributed.  Parameters are the
+ * effective ones (base values + offsets at the current global parameters).  USER atom order; host or device by out_is_device.
+ * The call behaves as an energy-only step behaves: it takes the current box and positions (with a bound context, posq through the same
+ * gather), follows the neighbour-list rules of any execute (a due rebuild happens, a pending side build is finished or cancelled as for an
+ * energy-only step), runs as plain launches -- it never captures or updates a step graph -- and counts in no timer sum and not in n_timed.
+ * It writes ONLY the table: the forces (snb_get_forces), the buffer of snb_set_force_output, a binding's force_buffer / energy_buffer /
+ * deriv_buffer and the engine's slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) stay bit for bit what they were.
+ * Host output returns after one synchronisation; device output is complete in stream order on snb_config.stream.
+ * Everything is checked before anything is enqueued: atom_energies NULL or both include flags 0: SNB_ERR_INVALID_ARGUMENT; shard_count > 1:
+ * SNB_ERR_UNSUPPORTED; SNB_Ewald with include_reciprocal (the k-sum of classic Ewald is not attributed; direct-only works):
+ * SNB_ERR_UNSUPPORTED; particles, box or positions missing: what snb_execute returns in that state.  The working memory (a table over the
+ * sorted atoms) is allocated at the first call: an engine that never calls pays nothing. */
+snb_status snb_evaluate_atom_energies(snb_handle h, int32_t include_direct, int32_t include_reciprocal,
+                                      double* atom_energies /* [n_atoms][n_subsets][2], USER order */, int32_t out_is_device);
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

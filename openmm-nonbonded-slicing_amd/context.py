@@ -319,6 +319,44 @@ class HipCalcSlicedNonbondedForceKernel:
             sl[mask == 0] = np.nan
         return sl
 
+    def computeAtomEnergies(self, context, includeDirect=True, includeReciprocal=True, devicePointer=None):
+        """Per-atom interaction energies with every subset (include/snb.h, snb_evaluate_atom_energies): ``A[i][J] = (Coulomb, vdW)`` raw
+        energy of atom i with all atoms of subset J at the context's positions, box and parameters, in one evaluation -- where a slice's
+        energy sits (which residues carry the ligand-protein Coulomb energy), without one subset and one PME mesh per residue.  Returns an
+        ndarray (N, n_subsets, 2) in user atom order, or None when ``devicePointer`` (address of a double [N][n_subsets][2] array on the
+        engine's device, complete in stream order) takes the table.  Not scaled by the lambdas; the long-range dispersion correction is a
+        per-slice constant and is not attributed.  Forces, force outputs and the slice energies of the last steps stay as they are."""
+        self._push_state(context)
+        if devicePointer is not None:
+            self._check(self._lib.snb_evaluate_atom_energies(self._h, int(bool(includeDirect)), int(bool(includeReciprocal)), ctypes.c_void_p(int(devicePointer)), 1))
+            return None
+        out = np.zeros((self.numParticles, self.numSubsets, 2))
+        self._check(self._lib.snb_evaluate_atom_energies(self._h, int(bool(includeDirect)), int(bool(includeReciprocal)), out.ctypes.data_as(ctypes.c_void_p), 0))
+        return out
+
+    @staticmethod
+    def sliceEnergiesFromAtomEnergies(table, subsets):
+        """The raw slice energies (S, 2) a per-atom table implies: E[slice(I, J)] = sum_{i in I} A[i][J] for I != J, and half that sum on
+        the diagonal, where every pair is counted from both ends.  The off-diagonal entry is taken from the larger subset index's atoms
+        (the other half of the table gives the same number)."""
+        table = np.asarray(table, dtype=np.float64); subsets = np.asarray(subsets)
+        n = table.shape[1]
+        out = np.zeros((n * (n + 1) // 2, 2))
+        for i in range(n):
+            rows = table[subsets == i].sum(axis=0)      # (n, 2): subset i's atoms with every subset
+            for j in range(i + 1):
+                out[sliceIndex(i, j)] = rows[j] * (0.5 if i == j else 1.0)
+        return out
+
+    @staticmethod
+    def groupAtomEnergies(table, groups):
+        """Sums of a per-atom table over lists of atom indices, one list per group (residue): (G, n_subsets, 2)."""
+        table = np.asarray(table, dtype=np.float64)
+        out = np.zeros((len(groups),) + table.shape[1:])
+        for g, atoms in enumerate(groups):
+            out[g] = table[np.asarray(list(atoms), dtype=np.int64)].sum(axis=0)
+        return out
+
     def computeSliceEnergiesForFrames(self, context, positions=None, boxes=None, slices=None, lambdaStates=None, positionsDevicePointer=None, numFrames=None):
         """Raw per-slice energies [F][S][2] of F stored frames in one call (include/snb.h, snb_evaluate_frames): the loop of an MBAR or
         reweighting pass over a trajectory, pipelined inside the engine -- the list of the next frame is built beside the step of this one.
@@ -477,6 +515,9 @@ class SlicedNonbondedForceImpl:
     def updateParametersInContext(self, context):
         self.kernel.copyParametersToContext(context, self.owner)
 
+    def getAtomEnergies(self, context, **options):
+        return self.kernel.computeAtomEnergies(context, **options)
+
 
 class System:
     def __init__(self):
@@ -564,6 +605,15 @@ class Context:
         for impl in self._impls:
             energy += impl.calcForcesAndEnergy(self, getForces, getEnergy or getParameterDerivatives, groups)
         return State(energy, self._forces.copy(), self._energyParamDerivs, self._parameters)
+
+    def getAtomEnergies(self, force, **options):
+        """Per-atom interaction energies of ``force`` with every subset, (N, n_subsets, 2): HipCalcSlicedNonbondedForceKernel.computeAtomEnergies."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        for impl in self._impls:
+            if impl.owner is force:
+                return impl.getAtomEnergies(self, **options)
+        raise OpenMMException("force not in this context")
 
     def _updateParametersInContext(self, force):
         for impl in self._impls:

@@ -15,6 +15,7 @@
 // per-pair slice arithmetic at all (the reference computes the slice index and loads LAMBDA[slice] per pair).
 #include "snb_internal.h"
 #include "switches.h"
+#include "pair_math.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <cstdlib>
@@ -26,48 +27,6 @@
 #endif
 namespace snb {
 
-// ---- math helpers -------------------------------------------------------------------------------
-__device__ inline float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
-// double: the hardware estimate (v_rsq_f64, ~2^-27) refined by two Newton steps -- about a third of the instructions of 1.0 / sqrt(x),
-// which runs its own refinements for the square root and again for the division; relative error < 1e-15 (tests hold 1e-12 on forces)
-__device__ inline double rsq(double x) {
-    double y = __builtin_amdgcn_rsq(x);
-    y = y * (1.5 - 0.5 * x * y * y);
-    y = y * (1.5 - 0.5 * x * y * y);
-    return y;
-}
-__device__ inline float fexp(float x) { return __expf(x); }
-__device__ inline double fexp(double x) { return exp(x); }
-// erfc(ar) given e = exp(-ar^2).  Single precision: Abramowitz & Stegun 7.1.26 (max abs error 1.5e-7), the
-// same approximation the reference GPU path uses (coulombLennardJones.cc:18-23); double: libm.
-__device__ inline float erfcFromExp(float ar, float e) {
-    float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * ar);
-    return (0.254829592f + (-0.284496736f + (1.421413741f + (-1.453152027f + 1.061405429f * t) * t) * t) * t) * t * e;
-}
-__device__ inline double erfcFromExp(double ar, double) { return erfc(ar); }
-// exp(-alpha^2 r^2): single precision folds log2(e) into the constant and issues one v_exp_f32
-__device__ inline float expNegAlpha2R2(float a2l2e, float, float r2) { return __builtin_amdgcn_exp2f(-a2l2e * r2); }
-__device__ inline double expNegAlpha2R2(double, double alpha, double r2) { return exp(-alpha * alpha * r2); }
-__device__ inline double erfOf(float ar, float) { return (double)erff(ar); }
-__device__ inline double erfOf(double ar, double) { return erf(ar); }
-// The Ewald exclusion correction's radial factor  g(x) = erf(x) - (2/sqrt(pi)) x exp(-x^2),  x = alpha r.  For small x the two terms
-// cancel to 0.752 x^3: in float, any error of erf (1.5e-7 absolute for Abramowitz & Stegun 7.1.26, an ulp for erff) is divided by x^2
-// there -- excluded partners a few picometres apart (a Drude particle on its core) were off by kJ/mol/nm.  Below x = 0.5 the series
-// (4/sqrt(pi)) x^3 sum_n (-1)^n x^(2n) / (n! (2n+3)), seven terms (truncation < 1e-7 relative), takes its place; double keeps libm erf.
-__device__ inline float exclusionG(float x, float e, double erfv) {
-    if (x < 0.5f) {
-        const float x2 = x * x;
-        const float s = 1.0f / 3 - x2 * (1.0f / 5 - x2 * (1.0f / 14 - x2 * (1.0f / 54 - x2 * (1.0f / 264 - x2 * (1.0f / 1560 - x2 * (1.0f / 10800))))));
-        return 2.2567583341910252f * x * x2 * s;
-    }
-    return (float)erfv - x * e * 1.1283791670955126f;
-}
-__device__ inline double exclusionG(double x, double e, double erfv) { return erfv - x * e * 1.1283791670955126; }
-
-__device__ inline void ldsAdd(float* p, float v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void ldsAdd(double* p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void gAdd(float* p, float v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void gAdd(double* p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // Force accumulation of atom slot `a`.  SNB_MIXED engines (P::fixed) keep the direct-space accumulators as 64-bit fixed point, 2^32 per
 // kJ/mol/nm, the way every GPU platform of the reference does (realToFixedPoint; CommonNonbondedSlicingKernels.cpp adds into
 // getLongForceBuffer, pme.cc:381-389): integer sums do not depend on the order in which waves arrive, so the force of a step is
@@ -84,11 +43,6 @@ template <bool FIXED, typename P> __device__ inline void fAddT(const P& p, float
     else gAdd(comp + a * p.fs, v);
 }
 
-__device__ inline double waveSum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Physical CU of the calling wave: XCC_ID[2:0] (hardware register 20) and the SE_ID | SH_ID | CU_ID bits 15:8 of HW_ID (register 4).
 // Used only to count co-resident work-groups of one launch (SNB_CU_SLOTS entries).
@@ -152,20 +106,6 @@ struct WorkClaim {
     }
 };
 
-__device__ inline int sliceOf(int a, int b) { return a > b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
-
-template <typename Real> __device__ inline void wrapDelta(Real& dx, Real& dy, Real& dz, const Real* box, const Real* inv) {
-    // OpenMM ReferenceForce::getDeltaRPeriodic (triclinic form)
-    Real s = floor(dz * inv[2] + Real(0.5)); dx -= s * box[6]; dy -= s * box[7]; dz -= s * box[8];
-    s = floor(dy * inv[1] + Real(0.5)); dx -= s * box[3]; dy -= s * box[4];
-    s = floor(dx * inv[0] + Real(0.5)); dx -= s * box[0];
-}
-
-// The sorted coordinates are box-wrapped per atom (imageOffset = wrapped - user).  Non-periodic exceptions
-// (periodicExceptions == false, ReferenceSlicedLJCoulombIxn.cpp:461-464) need the user's own coordinates back.
-template <typename Real> __device__ inline void unwrapDelta(Real& dx, Real& dy, Real& dz, const Real* off, int i, int j) {
-    dx -= off[3 * i] - off[3 * j]; dy -= off[3 * i + 1] - off[3 * j + 1]; dz -= off[3 * i + 2] - off[3 * j + 2];
-}
 
 // ---- cross-lane helpers -------------------------------------------------------------------------
 // DPP row_ror:1 -- every 16-lane row rotates by one lane (lane c receives the value of lane (c-1)&15).

@@ -110,6 +110,7 @@ struct EngineBase {
     virtual void setTimingInterval(int) = 0;
     virtual void getPme(double*, int32_t*, bool dispersion) = 0;
     virtual void evaluateFrames(const snb_frame_batch*) = 0;
+    virtual void evaluateAtomEnergies(int, int, double*, int) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
@@ -1560,11 +1561,10 @@ public:
         plan.ownSlabs = best; plan.ownMargin = M;
     }
 
-    void execute(int includeForces, int includeEnergy, int includeDirect, int includeRecip, double* energyOut) override {
-        if (includeEnergy == 2 && energyOut) { err = "snb_execute: include_energy == 2 (derivative-only step) delivers no total energy; pass energy = NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        const bool forces = includeForces != 0;
-        if (!forces && includeEnergy == 0) { if (energyOut) *energyOut = 0.0; return; }      // nothing asked for: nothing enqueued
-        if (forces) keptValid = false;      // (this step's forces replace the kept ones)
+    // What every evaluation starts with: the state checks, then the neighbour-list rules -- a due rebuild happens (in line, or as the exchange of a
+    // list built beside the steps), a side build nothing can use any more is cancelled, changed parameter values are refreshed.  forces: a forces
+    // step; anything else keeps the forces of the last forces step across a re-sort.  Returns whether the lists were rebuilt in line.
+    bool beginExecute(bool forces, int includeRecip) {
         if (!haveParticles) throw HipError{"snb_execute: particles were not set"};
         if (!havePositions) throw HipError{"snb_execute: positions were not set"};
         if (isPeriodic()) {
@@ -1601,6 +1601,27 @@ public:
         if ((valuesDirty || excValuesDirty) && !staticDirty && !rebuilding) refreshValues();
         if (rebuilding) { if (valuesDirty || excValuesDirty) { staticDirty = true; valuesDirty = excValuesDirty = false; } if (ctx.on) stageCtxPositions(ctxStage.p); rebuild(); }
         stepsSinceRebuild++;
+        return rebuilding;
+    }
+    // ... and ends with: the end-of-execute event of the displacement watch, the step count, the side build that falls due sw.sideLead executes from now
+    void endExecute() {
+        const bool autoMode = cfg.rebuild_interval < 0;
+        if (autoMode && cfg.neighbor_padding > 0) {
+            hipEvent_t& ev = evStepDone[stepCounter & 1];
+            if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            HIPCHECK(hipEventRecord(ev, stream));
+        }
+        stepCounter++;
+        // the rebuild that falls due sw.sideLead executes from now starts here, beside the steps, from the positions of the step just enqueued
+        if (!autoMode && stepsSinceRebuild == cfg.rebuild_interval - sw.sideLead && sideBuildPossible()) startSideBuild();
+    }
+
+    void execute(int includeForces, int includeEnergy, int includeDirect, int includeRecip, double* energyOut) override {
+        if (includeEnergy == 2 && energyOut) { err = "snb_execute: include_energy == 2 (derivative-only step) delivers no total energy; pass energy = NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const bool forces = includeForces != 0;
+        if (!forces && includeEnergy == 0) { if (energyOut) *energyOut = 0.0; return; }      // nothing asked for: nothing enqueued
+        if (forces) keptValid = false;      // (this step's forces replace the kept ones)
+        const bool rebuilding = beginExecute(forces, includeRecip);
         if (forces) outputWritten = outPtr != nullptr;      // (an energy-only step leaves the forces of the last forces step where they are)
         const bool energy = includeEnergy != 0;
         energySelective = includeEnergy == 2;      // derivative-only step: only the slices named by snb_set_energy_slices
@@ -1691,14 +1712,7 @@ public:
             if (sw.overlapDebug && sw.overlap && dOverlap.p && overlapDumps > 0) { overlapDumps--; dumpOverlapTable(); }
         }
         }      // forces step
-        if (autoMode && cfg.neighbor_padding > 0) {
-            hipEvent_t& ev = evStepDone[stepCounter & 1];
-            if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(ev, stream));
-        }
-        stepCounter++;
-        // the rebuild that falls due sw.sideLead executes from now starts here, beside the steps, from the positions of the step just enqueued
-        if (!autoMode && stepsSinceRebuild == cfg.rebuild_interval - sw.sideLead && sideBuildPossible()) startSideBuild();
+        endExecute();
         if (energy) {
             energyPending = true;
             if (energyOut) { fetchSliceEnergies(); double e = 0; for (int i = 0; i < 2 * S; i++) e += lambdas[i] * hostSliceE[i]; *energyOut = e; }      // (synchronises)
@@ -1898,6 +1912,45 @@ public:
         energyPending = false;
     }
 
+    // the pair kernels' view of the lists in use and of the method (p zeroed by the caller); the launch-specific fields stay with the caller
+    void fillDirect(DirectParams<Real>& p) {
+        p.posq = posq.p; p.sigeps = sigeps.p; p.blockSubset = blockSubset.p; p.workItems = workItems.p;
+        p.tileJ = tileJ.p; p.tileInfo = tileInfo.p; p.masks = masks.p; p.fx = fx.p; p.fy = fy.p; p.fz = fz.p; p.fs = fstride; p.fixed = fixedForces(); p.sliceE = sliceE.p; p.lambdas = dLambdas.p; p.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p;
+        const int r = cfg.shard_rank, c = cfg.shard_count;
+        (void)r; (void)c;
+        p.workStart = 0; p.workStride = 1; p.numWork = numWorkItems;      // the lists hold only the i-blocks this engine owns (block % shard_count == shard_rank)
+        p.nsub = nsub;
+        p.cutoff2 = (Real)(cfg.cutoff * cfg.cutoff);
+        p.krf = (Real)(std::pow(cfg.cutoff, -3.0) * (cfg.rf_dielectric - 1.0) / (2.0 * cfg.rf_dielectric + 1.0));
+        p.crf = (Real)((1.0 / cfg.cutoff) * (3.0 * cfg.rf_dielectric) / (2.0 * cfg.rf_dielectric + 1.0));
+        p.alpha = (Real)cfg.alpha; p.alphaD = (Real)cfg.alpha_d; p.k4pe = (Real)SNB_ONE_4PI_EPS0;
+        p.alpha2l2e = (Real)(cfg.alpha * cfg.alpha * 1.4426950408889634);
+        for (int i = 0; i <= EW_DEG; i++) p.ewPoly[i] = (Real)ewPoly[i];
+        for (int i = 0; i < 14; i++) p.ewPolyE[i] = (Real)ewPolyE[i];
+        for (int i = 0; i < 21; i++) p.dispPoly[i] = (Real)dispPoly[i];
+        p.ewScale = (Real)(2.0 / ewR2Max);
+        p.ewUsePoly = sw.ewaldErfc ? 0 : 1;
+        const double ic2 = 1.0 / (cfg.cutoff * cfg.cutoff), ic6 = ic2 * ic2 * ic2;
+        const double dar2 = cfg.alpha_d * cfg.alpha_d * cfg.cutoff * cfg.cutoff;
+        p.invCut6 = (Real)ic6; p.multShift6 = (Real)(ic6 * (1.0 - std::exp(-dar2) * (1.0 + dar2 + 0.5 * dar2 * dar2)));
+        p.useSwitch = useSwitch() ? 1 : 0; p.switchDist = (Real)cfg.switch_distance;
+        p.invSwitchWidth = (Real)(useSwitch() ? 1.0 / (cfg.cutoff - cfg.switch_distance) : 0.0);
+        for (int i = 0; i < 9; i++) p.box[i] = (Real)(gpuBuilt ? tileCell[i] : box[i]);
+        if (isPeriodic()) { p.invBoxDiag[0] = (Real)(1.0 / box[0]); p.invBoxDiag[1] = (Real)(1.0 / box[4]); p.invBoxDiag[2] = (Real)(1.0 / box[8]); }
+        p.boxDiag[0] = (Real)box[0]; p.boxDiag[1] = (Real)box[4]; p.boxDiag[2] = (Real)box[8];
+    }
+    // ... and of the O(N) pair lists: 1-4 exceptions and Ewald exclusion corrections
+    void fillPairLists(PairListParams<Real>& q) {
+        q.posq = posq.p; q.fx = fx.p; q.fy = fy.p; q.fz = fz.p; q.fs = fstride; q.fixed = fixedForces(); q.sliceE = sliceE.p; q.lambdas = dLambdas.p; q.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p;
+        const bool exPeriodic = (cfg.method == SNB_NoCutoff || cfg.method == SNB_CutoffNonPeriodic) ? false : cfg.exceptions_periodic != 0;
+        q.periodic = exPeriodic ? 1 : 0; q.imageOffset = imageOffset.p;
+        q.sigeps = sigeps.p; q.blockSubset = blockSubset.p; q.exclStart = exclStart.p; q.exclList = exclList.p; q.nSlices = S; q.sortedToUser = dSortedToUser.p; q.userToSorted = dUserToSorted.p;
+        for (int i = 0; i < 9; i++) q.box[i] = (Real)box[i];
+        q.alpha = (Real)cfg.alpha; q.alpha64 = cfg.alpha; q.alphaD = (Real)cfg.alpha_d; q.ljpme = cfg.method == SNB_LJPME;
+        q.pairs = pairs14.p; q.params = params14.p; q.n = n14;
+        q.nExclAtoms = (cfg.method >= SNB_Ewald && nExcl > 0) ? Npad : 0;
+    }
+
     // What a step does with forces: Full -- a forces step (accumulate, deliver to the force output); None -- an energy-only step (the
     // energy-only kernels: no force arithmetic, nothing cleared, nothing stored); Scratch -- the forces kernels into whatever set the views
     // point at, no delivery (energy-only steps of sharded PME engines).
@@ -1949,7 +2002,6 @@ public:
         if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream); }
         else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream);
         if (energy && Npad <= 0) launchZeroFill(sliceE.p, sizeof(double) * S * 2 * SNB_SLICE_E_PARTS, stream);      // (inside the step graph: a kernel, not a memset node)
-        const bool ew = cfg.method >= SNB_Ewald;
         // Opt-in (SNB_CONCURRENT_PME=1): forces-only graph steps run the reciprocal pipeline on a second stream beside the pair
         // kernel (disjoint force arrays fx.. / fpx..).  Timed (eager) steps stay serial so the per-kernel event timers stay clean.
         // overlapped step (see sw.overlap above): any graph step with both halves; needs the GPU-built work list (static item order is irrelevant)
@@ -1965,46 +2017,14 @@ public:
         std::memset(&q, 0, sizeof(q));
         // O(N) pair lists: one rank only when sharded -- the LAST one, which carries no PME grid once there are more ranks than grids
         const bool haveLists = includeDirect && cfg.shard_rank == cfg.shard_count - 1;
-        if (haveLists) {
-            q.posq = posq.p; q.fx = fx.p; q.fy = fy.p; q.fz = fz.p; q.fs = fstride; q.fixed = fixedForces(); q.sliceE = sliceE.p; q.lambdas = dLambdas.p; q.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p;
-            const bool exPeriodic = (cfg.method == SNB_NoCutoff || cfg.method == SNB_CutoffNonPeriodic) ? false : cfg.exceptions_periodic != 0;
-            q.periodic = exPeriodic ? 1 : 0; q.imageOffset = imageOffset.p;
-            q.sigeps = sigeps.p; q.blockSubset = blockSubset.p; q.exclStart = exclStart.p; q.exclList = exclList.p; q.nSlices = S; q.sortedToUser = dSortedToUser.p; q.userToSorted = dUserToSorted.p;
-            for (int i = 0; i < 9; i++) q.box[i] = (Real)box[i];
-            q.alpha = (Real)cfg.alpha; q.alpha64 = cfg.alpha; q.alphaD = (Real)cfg.alpha_d; q.ljpme = cfg.method == SNB_LJPME;
-            q.pairs = pairs14.p; q.params = params14.p; q.n = n14;
-            q.nExclAtoms = (ew && nExcl > 0) ? Npad : 0;
-        }
+        if (haveLists) fillPairLists(q);
         bool listsDone = !haveLists, kernelTimed = false, finished = false, energyFinished = false;
         DirectParams<Real> directB; int directMc = 0;      // overlapped step: the second launch of the tile kernel
         std::memset(&directB, 0, sizeof(directB));
         if (includeDirect) {
             DirectParams<Real> p;
             std::memset(&p, 0, sizeof(p));
-            p.posq = posq.p; p.sigeps = sigeps.p; p.blockSubset = blockSubset.p; p.workItems = workItems.p;
-            p.tileJ = tileJ.p; p.tileInfo = tileInfo.p; p.masks = masks.p; p.fx = fx.p; p.fy = fy.p; p.fz = fz.p; p.fs = fstride; p.fixed = fixedForces(); p.sliceE = sliceE.p; p.lambdas = dLambdas.p; p.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p;
-            const int r = cfg.shard_rank, c = cfg.shard_count;
-            (void)r; (void)c;
-            p.workStart = 0; p.workStride = 1; p.numWork = numWorkItems;      // the lists hold only the i-blocks this engine owns (block % shard_count == shard_rank)
-            p.nsub = nsub;
-            p.cutoff2 = (Real)(cfg.cutoff * cfg.cutoff);
-            p.krf = (Real)(std::pow(cfg.cutoff, -3.0) * (cfg.rf_dielectric - 1.0) / (2.0 * cfg.rf_dielectric + 1.0));
-            p.crf = (Real)((1.0 / cfg.cutoff) * (3.0 * cfg.rf_dielectric) / (2.0 * cfg.rf_dielectric + 1.0));
-            p.alpha = (Real)cfg.alpha; p.alphaD = (Real)cfg.alpha_d; p.k4pe = (Real)SNB_ONE_4PI_EPS0;
-            p.alpha2l2e = (Real)(cfg.alpha * cfg.alpha * 1.4426950408889634);
-            for (int i = 0; i <= EW_DEG; i++) p.ewPoly[i] = (Real)ewPoly[i];
-            for (int i = 0; i < 14; i++) p.ewPolyE[i] = (Real)ewPolyE[i];
-            for (int i = 0; i < 21; i++) p.dispPoly[i] = (Real)dispPoly[i];
-            p.ewScale = (Real)(2.0 / ewR2Max);
-            p.ewUsePoly = sw.ewaldErfc ? 0 : 1;
-            const double ic2 = 1.0 / (cfg.cutoff * cfg.cutoff), ic6 = ic2 * ic2 * ic2;
-            const double dar2 = cfg.alpha_d * cfg.alpha_d * cfg.cutoff * cfg.cutoff;
-            p.invCut6 = (Real)ic6; p.multShift6 = (Real)(ic6 * (1.0 - std::exp(-dar2) * (1.0 + dar2 + 0.5 * dar2 * dar2)));
-            p.useSwitch = useSwitch() ? 1 : 0; p.switchDist = (Real)cfg.switch_distance;
-            p.invSwitchWidth = (Real)(useSwitch() ? 1.0 / (cfg.cutoff - cfg.switch_distance) : 0.0);
-            for (int i = 0; i < 9; i++) p.box[i] = (Real)(gpuBuilt ? tileCell[i] : box[i]);
-            if (isPeriodic()) { p.invBoxDiag[0] = (Real)(1.0 / box[0]); p.invBoxDiag[1] = (Real)(1.0 / box[4]); p.invBoxDiag[2] = (Real)(1.0 / box[8]); }
-            p.boxDiag[0] = (Real)box[0]; p.boxDiag[1] = (Real)box[4]; p.boxDiag[2] = (Real)box[8];
+            fillDirect(p);
             const int mc = methodClass();
             const bool noFuse = sw.noFusedLists;
             p.stepTrace = traceThisStep ? dStepTrace.p : nullptr; p.traceSlot = 2;
@@ -2093,6 +2113,76 @@ public:
             if (includeDirect && (cfg.method == SNB_CutoffPeriodic || cfg.method == SNB_Ewald || cfg.method == SNB_PME)) { f.dispCoef = dDispCoef.p; f.invVolume = 1.0 / volume; }
         }
         return f;
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Per-atom interaction energies (snb_evaluate_atom_energies): the table A[i][J][t] of every atom with every subset.
+    // Behaves as an energy-only step behaves -- current box and positions (a binding's posq through the same gather), the neighbour-list
+    // rules of any execute, plain launches, no step graph, no timer -- and writes only the table: no force array, no force output, no bound
+    // buffer, neither the slice-energy partitions nor their sums.  Kernels: atomenergy.hip.  Reciprocal part: the UNMIXED pipeline with every
+    // mesh held (what a rank that owns all meshes runs), then the value part of the interpolation per (atom, mesh).
+    // ------------------------------------------------------------------------------------------
+    DevBuf<double> atomTab, atomOut;      // sorted-order working table [Npad][nsub][2]; user-order staging of a host result (both allocated at the first call)
+    void evaluateAtomEnergies(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
+        if (!out) { err = "snb_evaluate_atom_energies: atom_energies is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (!includeDirect && !includeRecip) { err = "snb_evaluate_atom_energies: neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (cfg.shard_count > 1) { err = "snb_evaluate_atom_energies: not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        if (cfg.method == SNB_Ewald && includeRecip) { err = "snb_evaluate_atom_energies: the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        beginExecute(false, includeRecip);
+        const size_t tabN = (size_t)Npad * nsub * 2, outN = (size_t)N * nsub * 2;
+        atomTab.resize(tabN);
+        if (!outIsDevice) atomOut.resize(outN);
+        double* const dst = outIsDevice ? out : atomOut.p;
+        launchZeroFill(atomTab.p, sizeof(double) * tabN, stream);
+        // the position-gather pass of a step that clears nothing: sorted positions, the Coulomb-mesh cells, the displacement watch
+        const bool recip = includeRecip && isPme() && nGrids > 0;
+        GatherCells<Real> gc;
+        std::memset(&gc, 0, sizeof(gc));
+        cellsFromGather = false; traceThisStep = false;
+        if (recip) {
+            PmeParams<Real> pp;
+            std::memset(&pp, 0, sizeof(pp));
+            fillPme(pp, pme, false);
+            if (pp.sortNcx > 0 && pp.colRange != nullptr) {
+                for (int i = 0; i < 9; i++) { gc.recip[i] = pp.recip[i]; gc.recipLo[i] = pp.recipLo[i]; }
+                gc.nx = pp.d.nx; gc.ny = pp.d.ny; gc.nz = pp.d.nz; gc.cells = pp.cells; gc.atomGrid = pp.atomGrid;
+                cellsFromGather = true;
+            }
+            if (dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
+        }
+        if (cfg.neighbor_padding > 0 && posRef.p) {
+            gc.posRef = posRef.p; gc.flags = dDispFlags;
+            const double half = 0.5 * cfg.neighbor_padding;
+            gc.fail2 = (Real)(half * half); gc.warn2 = (Real)(0.64 * half * half);
+        }
+        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream); }
+        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream);
+        if (includeDirect) {
+            DirectParams<Real> p; PairListParams<Real> q;
+            std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
+            fillDirect(p); fillPairLists(q);
+            launchAtomPairs<Real>(p, methodClass(), wrapMode, &q, atomTab.p, stream);
+        }
+        if (recip) {
+            PmeParams<Real> pp;
+            std::memset(&pp, 0, sizeof(pp));
+            fillPme(pp, pme, false); pp.mix = 0;
+            runPmeFront(pp, stream);
+            launchAtomPotential<Real>(pp, atomTab.p, stream);
+            if (cfg.method == SNB_LJPME) {
+                fillPme(pp, dpme, false); pp.mix = 0;
+                runPmeFront(pp, stream);
+                launchAtomPotential<Real>(pp, atomTab.p, stream);
+            }
+        }
+        SliceFinish f = makeSliceFinish(includeDirect != 0, includeRecip != 0);
+        f.dispCoef = nullptr;      // the long-range dispersion correction is a per-slice constant: not attributed
+        launchAtomFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, N, nsub, f, dst, stream);
+        endExecute();
+        if (!outIsDevice) {
+            HIPCHECK(hipMemcpyAsync(out, atomOut.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+        }
     }
 
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
@@ -2331,6 +2421,9 @@ snb_status snb_get_stats(snb_handle h, snb_stats* out) { if (!out) return SNB_ER
 snb_status snb_evaluate_frames(snb_handle h, const snb_frame_batch* b) {
     if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_frames: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
     return guard(h, [&] { h->impl->evaluateFrames(b); });
+}
+snb_status snb_evaluate_atom_energies(snb_handle h, int32_t includeDirect, int32_t includeRecip, double* atomEnergies, int32_t outIsDevice) {
+    return guard(h, [&] { h->impl->evaluateAtomEnergies(includeDirect, includeRecip, atomEnergies, outIsDevice); });
 }
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 

@@ -317,6 +317,11 @@ template <typename Real> void launchPairLists(const PairListParams<Real>& p, boo
 template <typename Real> bool launchDirectEnergy(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, hipStream_t s,
                                                  hipEvent_t evStart, hipEvent_t evStop, bool* timed);
 template <typename Real> void launchPairListsEnergy(const PairListParams<Real>& p, hipStream_t s);
+// per-atom interaction energies (atomenergy.hip, snb_evaluate_atom_energies): tab = double [Npad][nsub][2] over the sorted index, added to
+template <typename Real> void launchAtomPairs(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, double* tab, hipStream_t s);
+template <typename Real> void launchAtomPotential(const PmeParams<Real>& p, double* tab, hipStream_t s);   // + q_i psi_J(r_i) from the unmixed real-space potentials of p
+template <typename Real> void launchAtomFinish(const double* tab, const int* userToSorted, const int* blockSubset, const typename Vec<Real>::T4* posq, const typename Vec<Real>::T2* sigeps,
+                                               int nAtoms, int nsub, const SliceFinish& f, double* out, hipStream_t s);   // closed-form terms, sorted -> user order: out[nAtoms][nsub][2]
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s);   // 1: forward z FFT already done; 2: ... and the spectrum is plane-major (plane path)
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s);   // rebuild time: fills the plane path's kernel-value table
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s);   // after a spreader that returned 2: k_planeXY + k_fftZInvMix instead of forward FFT, convolution, inverse FFT
