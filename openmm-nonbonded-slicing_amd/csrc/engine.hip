@@ -703,7 +703,8 @@ public:
         if (verbose) fprintf(stderr, "[snb] rebuild: waited %.0f us for the queued steps, then %.0f us (host) for the build itself; device time %.0f us\n",
                              std::chrono::duration<double, std::micro>(tr1 - tr0).count(), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr1).count(), stats.last_rebuild_ms * 1e3);
         pmeCells.resize(Npad);   // per-slot scratch is sized here: nothing may allocate while a step is being captured into a graph
-        if (isPme()) { if (!dStrayCount.p) { dStrayCount.resize(2); HIPCHECK(hipMemsetAsync(dStrayCount.p, 0, 2 * sizeof(int), stream)); } planOwnSpread(pme); if (cfg.method == SNB_LJPME) planOwnSpread(dpme); planPlaneTable(pme); if (cfg.method == SNB_LJPME) planPlaneTable(dpme); }
+        if (isPme()) { if (!dStrayCount.p) { dStrayCount.resize(2); HIPCHECK(hipMemsetAsync(dStrayCount.p, 0, 2 * sizeof(int), stream)); } planOwnSpread(pme); if (cfg.method == SNB_LJPME) planOwnSpread(dpme); planPlaneTable(pme); if (cfg.method == SNB_LJPME) planPlaneTable(dpme);
+            if (verbose) { describeMesh("coulomb", pme); if (cfg.method == SNB_LJPME) describeMesh("dispersion", dpme); } }
         posRef.resize(Npad);
         HIPCHECK(hipMemcpyAsync(posRef.p, posq.p, sizeof(T4) * (size_t)Npad, hipMemcpyDeviceToDevice, stream));
         if (hDispFlags[1]) listOverruns++;      // an atom had moved more than skin/2 before this rebuild came
@@ -1527,6 +1528,18 @@ public:
         plan.planeEtermFilled = launchPlaneEterm<Real>(pp, plan.planeEterm.p, stream);
         plan.planeEtermReady = true;
     }
+    // SNB_VERBOSE: the spreader planned for a mesh at this rebuild.  Sort columns and bricks decide between the atomic spreader and the brick
+    // kernels for good; the own-atoms spreader is only planned here -- launchSpreadOwn (pme.hip) can still decline it at the launch, and
+    // that it ran shows only where the plane path follows it (no y-pass stamps in slots 3 / 5).
+    void describeMesh(const char* name, const PmePlan<Real>& plan) const {
+        int ncx = 0, ncy = 0, gx = 0, gy = 0;
+        const bool bricks = nGrids > 0 && brickGeometry(plan, ncx, ncy, gx, gy);
+        // (the sort columns are cut on the Coulomb mesh, `pme`, for every mesh; the mesh size and the bricks are this plan's)
+        fprintf(stderr, "[snb] %s mesh %d x %d x %d: sort columns %d x %d of %d x %d cells, %s", name, plan.d.nx, plan.d.ny, plan.d.nz,
+                colCells[0] > 0 ? pme.d.nx / colCells[0] : 0, colCells[0] > 0 ? pme.d.ny / colCells[1] : 0, colCells[0], colCells[1],
+                !bricks ? "atomic spreader\n" : "");
+        if (bricks) fprintf(stderr, "bricks of %d x %d columns, %s (slabs %d, margin %d)\n", gx, gy, plan.ownSlabs > 0 ? "own-atoms spreader planned" : "scanning brick spreader", plan.ownSlabs, plan.ownMargin);
+    }
     void planOwnSpread(PmePlan<Real>& plan) {
         plan.ownSlabs = 0;
         int ncx, ncy, gx, gy;
@@ -1541,7 +1554,7 @@ public:
         const size_t accBytes = fixed ? 4 : 8;
         const int cx = gx * (plan.d.nx / ncx), cy = gy * (plan.d.ny / ncy), nz = plan.d.nz;
         const int RX = cx + 4 + 2 * M, RY = cy + 4 + 2 * M;
-        if (RX > plan.d.nx || RY > plan.d.ny || gx * gy > 16 || nz > 256) return;
+        if (RX > plan.d.nx || RY > plan.d.ny || gx * gy > 16 || nz > 256) return;      // (nz > 256 ends here: launchSpreadOwn's own test of it is never reached)
         int best = 0;
         const int forced = sw.ownSlabs;
         for (int pass = 0; pass < 2 && !best; pass++)

@@ -32,6 +32,11 @@ TOLS = {"single": 1e-3, "mixed": 1e-3, "double": 1e-5}
 SHELL_LO = 0.9                          # the shell is 0.9 rc <= r < rc
 MARGIN = 3.0                            # every shell pair must clear MARGIN * tol * max(|Fi|, |Fj|, 1)
 TRICLINIC = np.array([[6.0, 0.0, 0.0], [1.5, 6.0, 0.0], [-1.2, 2.0, 6.0]])
+# cells with three unequal lengths (every other cell of the suite has one length on all three axes): the sites of their lattices are counted
+# per axis so that the spacing is the same along each, 0.2667 nm
+ORTHO_LENGTHS = (5.6, 6.4, 7.2)
+ORTHO_SITES = (21, 24, 27)
+TRICLINIC_UNEQUAL = np.array([[5.6, 0.0, 0.0], [1.4, 6.4, 0.0], [-1.2, 2.0, 7.2]])
 
 
 def _orc():
@@ -209,6 +214,30 @@ def _lattice(name, n, L, nsub, seed, jitter=0.05):
     return make_system(name, pos, np.diag([L, L, L]), _charges(n, rng), _slabs(pos, L, nsub), nsub)
 
 
+def lattice_sites(sites, lengths, rng, jitter=0.05):
+    """mx x my x mz jittered sites in a cell of Lx x Ly x Lz (systems.jittered_lattice assumes a cube); z runs fastest."""
+    m = np.asarray(sites); L = np.asarray(lengths, dtype=np.float64)
+    g = np.stack(np.meshgrid(np.arange(m[0]), np.arange(m[1]), np.arange(m[2]), indexing="ij"), -1).reshape(-1, 3)
+    return (g + 0.5) * (L / m) + rng.uniform(-jitter, jitter, (len(g), 3))
+
+
+def orthorhombic():
+    """13 608 atoms on 21 x 24 x 27 sites in 5.6 x 6.4 x 7.2 nm (52.7 / nm^3), three slab subsets along y: no two faces are the same
+    distance apart, and the subset borders run across the sort columns' other axis."""
+    rng = np.random.default_rng(111)
+    pos = lattice_sites(ORTHO_SITES, ORTHO_LENGTHS, rng)
+    sub = np.minimum((np.mod(pos[:, 1], ORTHO_LENGTHS[1]) / ORTHO_LENGTHS[1] * 3).astype(int), 2)
+    return make_system("orthorhombic", pos, np.diag(ORTHO_LENGTHS), _charges(len(pos), rng), sub, 3)
+
+
+def triclinic_unequal():
+    """The same lattice sheared with a reduced cell whose three diagonal entries differ."""
+    rng = np.random.default_rng(112)
+    pos = lattice_sites(ORTHO_SITES, ORTHO_LENGTHS, rng)
+    sub = _slabs(pos, ORTHO_LENGTHS[0], 3)
+    return make_system("triclinic_unequal", (pos / np.asarray(ORTHO_LENGTHS)) @ TRICLINIC_UNEQUAL, TRICLINIC_UNEQUAL, _charges(len(pos), rng), sub, 3)
+
+
 def lattice_dense():
     """13 824 atoms, L = 6 nm (64 / nm^3), three slab subsets."""
     return _lattice("lattice_dense", 13824, 6.0, 3, 101)
@@ -298,7 +327,7 @@ def unwrapped():
 GEOMETRIES = {
     "lattice_dense": lattice_dense, "lattice_dilute": lattice_dilute, "water_density": water_density, "blob_in_gas": blob_in_gas,
     "sparse_subsets": sparse_subsets, "triclinic": triclinic, "small_box": small_box, "tiny_63": lambda: tiny(63), "tiny_64": lambda: tiny(64),
-    "tiny_65": lambda: tiny(65), "tiny_97": lambda: tiny(97), "nonperiodic_cloud": nonperiodic_cloud, "unwrapped": unwrapped,
+    "tiny_65": lambda: tiny(65), "tiny_97": lambda: tiny(97), "nonperiodic_cloud": nonperiodic_cloud, "unwrapped": unwrapped, "orthorhombic": orthorhombic, "triclinic_unequal": triclinic_unequal,
 }
 
 
@@ -612,6 +641,7 @@ class Engine:
         cfg.cutoff = s["rc"] if cutoff is None else cutoff; cfg.rf_dielectric = 1.0; cfg.exceptions_periodic = int(s["exceptions_periodic"])
         cfg.neighbor_padding = padding; cfg.rebuild_interval = interval; cfg.shard_rank = rank; cfg.shard_count = world
         cfg.host_neighbor_build = host_build
+        self.configure(cfg)
         self.ok(self.L.snb_create(ctypes.byref(cfg), ctypes.byref(self.h)), create=True)
         ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         self.ok(self.L.snb_set_particles(self.h, _dp(s["q"]), _dp(s["sigma"]), _dp(s["epsilon"]), ip(s["subset"])))
@@ -622,6 +652,11 @@ class Engine:
             self.ok(self.L.snb_set_exceptions(self.h, 0, None, None, None, None, None))
         self.ok(self.L.snb_set_lambdas(self.h, _dp(np.ascontiguousarray(s["lam"]))))
         self.set_frame(s)
+
+    direct, recip = 1, 1          # include_direct, include_reciprocal of every step (tests/recip_systems.py evaluates the reciprocal part alone)
+
+    def configure(self, cfg):
+        """Further fields of the snb_config before snb_create (the Ewald / PME parameters of tests/recip_systems.py)."""
 
     def ok(self, st, create=False):
         if st != 0:
@@ -660,16 +695,16 @@ class Engine:
     def step_energy_forces(self):
         """An energy + forces step: (forces, raw slice energies -- the dE/dlambda of every slice --, total energy)."""
         e = ctypes.c_double(0.0)
-        self.ok(self.L.snb_execute(self.h, 1, 1, 1, 1, ctypes.byref(e)))
+        self.ok(self.L.snb_execute(self.h, 1, 1, self.direct, self.recip, ctypes.byref(e)))
         return self.forces(), self.slice_energies(), e.value
 
     def step_forces(self):
         """A forces-only step (the second one onward replays the captured graph)."""
-        self.ok(self.L.snb_execute(self.h, 1, 0, 1, 1, None))
+        self.ok(self.L.snb_execute(self.h, 1, 0, self.direct, self.recip, None))
         return self.forces()
 
     def step_energy_only(self):
-        self.ok(self.L.snb_execute(self.h, 0, 1, 1, 1, None))
+        self.ok(self.L.snb_execute(self.h, 0, 1, self.direct, self.recip, None))
         return self.slice_energies()
 
     def stats(self):
