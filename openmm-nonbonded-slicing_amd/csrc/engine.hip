@@ -8,6 +8,7 @@
 #include "../../include/snb.h"
 #include "snb_internal.h"
 #include "switches.h"
+#include "host_lists.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -53,11 +54,12 @@ template <typename T> struct DevBuf {
         n = m > 0 ? m : 1;
         HIPCHECK(hipMalloc((void**)&p, sizeof(T) * n));
     }
-    void upload(const std::vector<T>& h, hipStream_t s) {
-        resize(h.size());
-        if (!h.empty()) HIPCHECK(hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s));
-    }
+    void upload(const T* h, size_t count, hipStream_t s) { resize(count); if (count > 0) HIPCHECK(hipMemcpyAsync(p, h, sizeof(T) * count, hipMemcpyHostToDevice, s)); }
+    void upload(const std::vector<T>& h, hipStream_t s) { upload(h.data(), h.size(), s); }
 };
+static_assert(sizeof(Int4) == sizeof(int4) && sizeof(Int2) == sizeof(int2), "host_lists.h names int4 / int2 without HIP; its records are uploaded as such");
+inline void upload(DevBuf<int4>& d, const std::vector<Int4>& h, hipStream_t s) { d.upload(reinterpret_cast<const int4*>(h.data()), h.size(), s); }
+inline void upload(DevBuf<int2>& d, const std::vector<Int2>& h, hipStream_t s) { d.upload(reinterpret_cast<const int2*>(h.data()), h.size(), s); }
 
 // Small asynchronous host-to-device updates (lambdas, energy-slice mask, dispersion coefficients, global parameter values) go through a ring
 // of pinned slots, one per in-flight update, each guarded by an event: the setter's own vector may be overwritten by the next call while an
@@ -290,7 +292,6 @@ public:
     int lastPadCount = 0;      // the exact padded count of the last accepted build (what a frame batch sizes its own prediction from)
     int npadPredict = 0; long long padMispredictions = 0;      // > 0: size of the padded arrays the next GPU rebuild assumes (gpuRebuild); how often that was too small
     int Npad = 0, numBlocks = 0; int64_t numTiles = 0, numMaskTiles = 0, shardTiles = 0; bool wrapMode = false;
-    std::vector<int> sortedToUser, userToSorted;
     DevBuf<T4> posq; DevBuf<T2> sigeps; DevBuf<Real> forceBuf, imageOffset, dLambdas;
     struct FView { Real* p = nullptr; } fx, fy, fz, fpx, fpy, fpz;   // views of forceBuf (7 Npad values, cleared by the position-gather pass)
     int fstride = 1;      // index stride of an atom in the direct-space accumulators (three arrays fx | fy | fz: 1)
@@ -357,9 +358,10 @@ public:
     DevBuf<Real> dFixScale;      // [4]: fixed-point scale and its inverse of the charge mesh, then of the dispersion mesh
     DevBuf<int> dSortedToUser, dUserToSorted, blockSubset, tileJ, atomSubset, atomGrid, gridSubset, exclStart, exclList;
     // GPU neighbour build: static user-order data and scratch
-    DevBuf<int> dUSubset, dSubsetStart, dSubsetPaddedStart, dSlotOfSubset, dValsIn, dValsOut, dCounters; DevBuf<Real> dUCharge, dWrapped, dOffsetU; DevBuf<T2> dUSigEps;
-    DevBuf<unsigned char> dPadFlag, dSortTemp; DevBuf<unsigned long long> dKeysIn, dKeysOut; DevBuf<float> dBlockCenter, dBlockHalf;
-    std::vector<int> hSubsetStart, hSubsetPaddedStart, staticBlkSubset; int staticNpad = 0; size_t tileCap = 0; bool staticDirty = true, gpuBuilt = false;
+    DevBuf<int> dUSubset, dSlotOfSubset, dValsIn, dValsOut, dCounters; DevBuf<Real> dUCharge, dWrapped, dOffsetU; DevBuf<T2> dUSigEps;
+    DevBuf<unsigned char> dSortTemp; DevBuf<unsigned long long> dKeysIn, dKeysOut; DevBuf<float> dBlockCenter, dBlockHalf;
+    std::vector<int> hExclStart, hExclList, hSlotOfSubset;      // uploadStatic's host copies of exclStart / exclList / dSlotOfSubset, for the host builder
+    size_t tileCap = 0; bool staticDirty = true, gpuBuilt = false;
     DevBuf<int2> pairs14, pairsExcl, colRange; DevBuf<int4> tileInfo, workItems, workItemsStage, workItemsPartial; int numWorkItems = 0; int colCells[2] = {0, 0}; DevBuf<unsigned> masks;
     DevBuf<T4> params14, paramsExcl; int n14 = 0, nExcl = 0;
     DevBuf<int> dSliceNeedAll, dSliceNeedSel; std::vector<int> sliceNeedSel;      // energy steps: every slice / the slices a derivative-only step (include_energy == 2) must produce
@@ -371,7 +373,6 @@ public:
     // direct-space ownership: i-block I belongs to this engine when I % shardPeriod lies in [shardBegin, shardEnd); the default is
     // (shard_rank, shard_rank + 1, shard_count); snb_set_shard_blocks lets the host rebalance direct-space work between ranks
     int shardBegin = 0, shardEnd = 1, shardPeriod = 1;
-    bool ownsBlock(int b) const { const int r = b % shardPeriod; return r >= shardBegin && r < shardEnd; }
     void setShardBlocks(int begin, int end, int period) override {
         if (period < 1 || begin < 0 || end < begin || end > period) throw std::runtime_error("snb_set_shard_blocks: need 0 <= begin <= end <= period");
         if (begin == shardBegin && end == shardEnd && period == shardPeriod) return;
@@ -687,10 +688,9 @@ public:
     void sync() override { HIPCHECK(hipStreamSynchronize(stream)); }
 
     // ------------------------------------------------------------------------------------------
-    // Neighbour structure: sort, blocks, per-atom gathered j-tiles, exclusion masks (host, v1).
+    // Neighbour structure: sort, blocks, per-atom gathered j-tiles, exclusion masks.  The host builder itself is host_lists.h
+    // (buildHostLists): hostRebuild brings the positions and effective parameters back from the device and sends the lists up.
     // ------------------------------------------------------------------------------------------
-    static inline bool owns(int I, int J) { return ((I + J) & 1) ? (I > J) : (I < J); }
-
     void rebuild() {
         const bool verbose = sw.verbose;
         const auto tr0 = std::chrono::steady_clock::now();
@@ -715,296 +715,47 @@ public:
     void hostRebuild() {
         auto t0 = std::chrono::steady_clock::now();
         if (ctx.on) HIPCHECK(hipStreamSynchronize(stream));      // (the user-order copy of the bound positions was staged on the engine's stream)
-        // 1. host copy of the user positions
         std::vector<double> hp((size_t)N * 3);
-        {
+        auto fetch = [&](auto type) {
             const int st = posStride4 ? 4 : 3;
-            if (posIsDouble) {
-                std::vector<double> tmp((size_t)N * st);
-                HIPCHECK(hipMemcpy(tmp.data(), devUserPos, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
-                for (int i = 0; i < N; i++) for (int d = 0; d < 3; d++) hp[3 * (size_t)i + d] = tmp[(size_t)i * st + d];
-            } else {
-                std::vector<float> tmp((size_t)N * st);
-                HIPCHECK(hipMemcpy(tmp.data(), devUserPos, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
-                for (int i = 0; i < N; i++) for (int d = 0; d < 3; d++) hp[3 * (size_t)i + d] = tmp[(size_t)i * st + d];
-            }
-        }
-        const bool periodic = isPeriodic();
-        const double R = (cfg.method == SNB_NoCutoff) ? 1e300 : cfg.cutoff + cfg.neighbor_padding;
-        const bool rect = box[3] == 0 && box[6] == 0 && box[7] == 0;
-        // 2. wrap into the primary cell (fractional coordinates; lower-triangular box)
-        std::vector<double> wp(hp), off((size_t)N * 3, 0.0);
-        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-        if (periodic) {
-            for (int i = 0; i < N; i++) {
-                double* x = &wp[3 * (size_t)i];
-                double s2 = std::floor(x[2] / box[8]); x[0] -= s2 * box[6]; x[1] -= s2 * box[7]; x[2] -= s2 * box[8];
-                double s1 = std::floor(x[1] / box[4]); x[0] -= s1 * box[3]; x[1] -= s1 * box[4];
-                double s0 = std::floor(x[0] / box[0]); x[0] -= s0 * box[0];
-                for (int d = 0; d < 3; d++) off[3 * (size_t)i + d] = x[d] - hp[3 * (size_t)i + d];
-            }
-            lo[0] = lo[1] = lo[2] = 0; hi[0] = box[0]; hi[1] = box[4]; hi[2] = box[8];
-            if (!rect) { lo[0] = std::min(0.0, box[3]) + std::min(0.0, box[6]); hi[0] = box[0] + std::max(0.0, box[3]) + std::max(0.0, box[6]); lo[1] = std::min(0.0, box[7]); hi[1] = box[4] + std::max(0.0, box[7]); }
-        } else {
-            for (int i = 0; i < N; i++) for (int d = 0; d < 3; d++) { lo[d] = std::min(lo[d], wp[3 * (size_t)i + d]); hi[d] = std::max(hi[d], wp[3 * (size_t)i + d]); }
-            if (N == 0) { lo[0] = lo[1] = lo[2] = 0; hi[0] = hi[1] = hi[2] = 1; }
-            for (int d = 0; d < 3; d++) { hi[d] += 1e-6 + 1e-9 * std::fabs(hi[d]); }
-        }
-        double ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
-        for (int d = 0; d < 3; d++) if (!(ext[d] > 1e-9)) ext[d] = 1e-9;
-        // 3. sort: (subset, serpentine xy column, z up/down)
-        const double volume = ext[0] * ext[1] * ext[2];
-        const double aTarget = std::cbrt(32.0 * volume / std::max(N, 1));
-        int ncx = std::max(1, std::min(2048, (int)std::lround(ext[0] / aTarget)));
-        int ncy = std::max(1, std::min(2048, (int)std::lround(ext[1] / aTarget)));
-        // With PME on a rectangular box the sort columns are made commensurate with the mesh (whole grid cells, >= 5 wide),
-        // so the same sorted order feeds the brick-spreading kernel (pme.hip k_spreadBrick).
-        colCells[0] = colCells[1] = 0;
-        if (isPme() && rect && nGrids > 0) {
-            auto pick = [&](int n, double L) {
-                int best = 0; double bestErr = 1e300;
-                for (int d = 5; d <= 16 && d <= n; d++) if (n % d == 0) { double e = std::fabs(d * L / n - aTarget); if (e < bestErr) { bestErr = e; best = d; } }
-                return best;
-            };
-            const int px = pick(pme.d.nx, box[0]), py = pick(pme.d.ny, box[4]);
-            const size_t brickBytes = sizeof(double) * (size_t)px * py * pme.d.nz;
-            if (px > 0 && py > 0 && brickBytes <= 60 * 1024 && std::max(pme.d.nx, std::max(pme.d.ny, pme.d.nz)) < 1024) {      // (the packed mesh cell of an atom holds 10 bits per axis)
-            colCells[0] = px; colCells[1] = py; ncx = pme.d.nx / px; ncy = pme.d.ny / py; }
-        }
-        std::vector<uint64_t> key(N);
-        std::vector<int> colOfAtom(N);
-        for (int i = 0; i < N; i++) {
-            const double* x = &wp[3 * (size_t)i];
-            int cx = std::min(ncx - 1, std::max(0, (int)((x[0] - lo[0]) / ext[0] * ncx)));
-            int cy = std::min(ncy - 1, std::max(0, (int)((x[1] - lo[1]) / ext[1] * ncy)));
-            colOfAtom[i] = cx * ncy + cy;
-            int col = cx * ncy + ((cx & 1) ? (ncy - 1 - cy) : cy);
-            double zf = std::min(1.0, std::max(0.0, (x[2] - lo[2]) / ext[2]));
-            if (col & 1) zf = 1.0 - zf;
-            uint64_t zq = (uint64_t)(zf * 1048575.0);
-            key[i] = ((uint64_t)subset[i] << 44) | ((uint64_t)col << 20) | zq;
-        }
-        std::vector<int> order(N);
-        std::iota(order.begin(), order.end(), 0);
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return key[a] != key[b] ? key[a] < key[b] : a < b; });
-        sortedToUser.clear(); userToSorted.assign(N, -1);
-        std::vector<int> blkSubset;
-        {
-            size_t k = 0;
-            for (int s = 0; s < nsub; s++) {
-                size_t start = sortedToUser.size();
-                while (k < (size_t)N && subset[order[k]] == s) { userToSorted[order[k]] = (int)sortedToUser.size(); sortedToUser.push_back(order[k]); k++; }
-                while ((sortedToUser.size() - start) % 32) sortedToUser.push_back(-1);
-                for (size_t b = start / 32; b < sortedToUser.size() / 32; b++) blkSubset.push_back(s);
-            }
-        }
-        Npad = (int)sortedToUser.size(); numBlocks = Npad / 32;
-        if (colCells[0] > 0) {   // sorted range of every (subset, column): atoms of one column are contiguous in the sorted order
-            const int ncol = ncx * ncy;
-            std::vector<int2> hRange((size_t)nsub * ncol, make_int2(0, 0));
-            for (int s = 0; s < Npad; s++) {
-                const int u = sortedToUser[s]; if (u < 0) continue;
-                int2& rg = hRange[(size_t)subset[u] * ncol + colOfAtom[u]];
-                if (rg.y == 0) rg.x = s;
-                rg.y = s + 1;
-            }
-            colRange.upload(hRange, stream);
-        }
-        if (Npad >= (1 << SNB_JSHIFT_BITS) - 1) throw HipError{"too many atoms for the 25-bit tile index"};
-        // 4. sorted parameter arrays (effective parameter values: formed on the device, fetched for this host-side path)
+            std::vector<decltype(type)> tmp((size_t)N * st);
+            HIPCHECK(hipMemcpy(tmp.data(), devUserPos, sizeof(type) * tmp.size(), hipMemcpyDeviceToHost));
+            for (int i = 0; i < N; i++) for (int d = 0; d < 3; d++) hp[3 * (size_t)i + d] = tmp[(size_t)i * st + d];
+        };
+        if (posIsDouble) fetch(double()); else fetch(float());
+        HostListInput in;
+        in.n = N; in.nsub = nsub; in.subset = subset.data(); in.pos = hp.data();
+        for (int i = 0; i < 9; i++) in.box[i] = box[i];
+        in.periodic = isPeriodic(); in.noCutoff = cfg.method == SNB_NoCutoff; in.listRadius = cfg.cutoff + cfg.neighbor_padding;
+        if (isPme() && nGrids > 0) { in.mesh[0] = pme.d.nx; in.mesh[1] = pme.d.ny; in.mesh[2] = pme.d.nz; }
+        in.exclStart = hExclStart.data(); in.exclList = hExclList.data(); in.slotOfSubset = hSlotOfSubset.data();
+        in.shardBegin = shardBegin; in.shardEnd = shardEnd; in.shardPeriod = shardPeriod;
+        const HostLists L = buildHostLists(in);
+        Npad = L.npad; numBlocks = L.numBlocks; wrapMode = L.wrapMode; colCells[0] = L.colCells[0]; colCells[1] = L.colCells[1];
+        numTiles = L.numTiles; numMaskTiles = L.numMaskTiles; shardTiles = L.shardTiles; numWorkItems = (int)L.workItems.size();
+        if (Npad >= (1 << SNB_JSHIFT_BITS) - 1) throw HipError{"too many atoms for the 25-bit tile index"};      // (L's tile entries are then garbage; nothing of L has been uploaded)
+        // sorted parameter arrays (effective parameter values: formed on the device, fetched for this host-side path)
         std::vector<Real> effQ(N); std::vector<T2> effSE(N);
         if (N > 0) { HIPCHECK(hipMemcpy(effQ.data(), dUCharge.p, sizeof(Real) * N, hipMemcpyDeviceToHost)); HIPCHECK(hipMemcpy(effSE.data(), dUSigEps.p, sizeof(T2) * N, hipMemcpyDeviceToHost)); }
         std::vector<T4> hPosq(Npad); std::vector<T2> hSigeps(Npad); std::vector<Real> hOff((size_t)Npad * 3, Real(0));
-        std::vector<int> hAtomSubset(Npad, -1), hAtomGrid(Npad, -1);
-        std::vector<int> slotOfSubset(nsub, -1);
-        if (cfg.shard_count == 1) std::iota(slotOfSubset.begin(), slotOfSubset.end(), 0);
-        else for (size_t g = 0; g < ownedSubsets.size(); g++) slotOfSubset[ownedSubsets[g]] = (int)g;
         for (int s = 0; s < Npad; s++) {
-            int u = sortedToUser[s];
+            const int u = L.sortedToUser[s];
             if (u >= 0) {
-                hPosq[s].x = (Real)wp[3 * (size_t)u]; hPosq[s].y = (Real)wp[3 * (size_t)u + 1]; hPosq[s].z = (Real)wp[3 * (size_t)u + 2]; hPosq[s].w = effQ[u];
+                hPosq[s].x = (Real)L.wrapped[3 * (size_t)u]; hPosq[s].y = (Real)L.wrapped[3 * (size_t)u + 1]; hPosq[s].z = (Real)L.wrapped[3 * (size_t)u + 2]; hPosq[s].w = effQ[u];
                 hSigeps[s] = effSE[u];
-                for (int d = 0; d < 3; d++) hOff[3 * (size_t)s + d] = (Real)off[3 * (size_t)u + d];
-                hAtomSubset[s] = subset[u]; hAtomGrid[s] = slotOfSubset[subset[u]];
+                for (int d = 0; d < 3; d++) hOff[3 * (size_t)s + d] = (Real)L.imageOffset[3 * (size_t)u + d];
             } else {   // parked padding atom: zero parameters, far away, distinct
                 hPosq[s].x = (Real)(1e9 + 1e6 * (s & 4095)); hPosq[s].y = (Real)2e9; hPosq[s].z = (Real)-3e9; hPosq[s].w = 0;
                 hSigeps[s].x = 0; hSigeps[s].y = 0;
             }
         }
-        // 5. block bounding boxes (real atoms only)
-        std::vector<double> bc((size_t)numBlocks * 3, 0.0), bh((size_t)numBlocks * 3, 0.0);
-        double maxFullExt[3] = {0, 0, 0};
-        for (int b = 0; b < numBlocks; b++) {
-            double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-            for (int k = 0; k < 32; k++) {
-                int u = sortedToUser[b * 32 + k]; if (u < 0) continue;
-                for (int d = 0; d < 3; d++) { mn[d] = std::min(mn[d], wp[3 * (size_t)u + d]); mx[d] = std::max(mx[d], wp[3 * (size_t)u + d]); }
-            }
-            for (int d = 0; d < 3; d++) { bc[3 * (size_t)b + d] = 0.5 * (mn[d] + mx[d]); bh[3 * (size_t)b + d] = 0.5 * (mx[d] - mn[d]); maxFullExt[d] = std::max(maxFullExt[d], mx[d] - mn[d]); }
-        }
-        // 6. tiles
-        wrapMode = false;
-        bool allPairs = (cfg.method == SNB_NoCutoff);
-        if (periodic) {
-            if (!rect) { wrapMode = true; allPairs = true; }
-            else for (int d = 0; d < 3; d++) if (!(maxFullExt[d] + 2 * R < box[4 * d])) { wrapMode = true; allPairs = true; }
-        }
-        std::vector<int> hTileJ; std::vector<int4> hTileInfo; std::vector<int2> hBlockTiles(numBlocks);
-        std::vector<unsigned> hMasks;
-        // exclusion CSR over user indices
-        std::vector<int> exStart(N + 1, 0), exList;
-        {
-            const size_t m = excPairs.size() / 2;
-            for (size_t k = 0; k < m; k++) { exStart[excPairs[2 * k] + 1]++; exStart[excPairs[2 * k + 1] + 1]++; }
-            for (int i = 0; i < N; i++) exStart[i + 1] += exStart[i];
-            exList.resize(exStart[N]);
-            std::vector<int> fill(N, 0);
-            for (size_t k = 0; k < m; k++) { int a = excPairs[2 * k], b = excPairs[2 * k + 1]; exList[exStart[a] + fill[a]++] = b; exList[exStart[b] + fill[b]++] = a; }
-        }
-        // cell grid over sorted real atoms (rectangular domains only; allPairs mode does not need it)
-        int nc[3] = {1, 1, 1}; std::vector<int> cellStart, cellAtoms;
-        double csz[3] = {ext[0], ext[1], ext[2]};
-        if (!allPairs) {
-            const double target = std::max(aTarget, R / 3.0);
-            for (int d = 0; d < 3; d++) { nc[d] = std::max(1, std::min(512, (int)(ext[d] / target))); csz[d] = ext[d] / nc[d]; }
-            const size_t ncell = (size_t)nc[0] * nc[1] * nc[2];
-            cellStart.assign(ncell + 1, 0);
-            std::vector<int> cellOf(Npad, -1);
-            for (int s = 0; s < Npad; s++) {
-                int u = sortedToUser[s]; if (u < 0) continue;
-                int c[3];
-                for (int d = 0; d < 3; d++) c[d] = std::min(nc[d] - 1, std::max(0, (int)((wp[3 * (size_t)u + d] - lo[d]) / csz[d])));
-                cellOf[s] = (c[0] * nc[1] + c[1]) * nc[2] + c[2];
-                cellStart[cellOf[s] + 1]++;
-            }
-            for (size_t c = 0; c < ncell; c++) cellStart[c + 1] += cellStart[c];
-            cellAtoms.resize(cellStart[ncell]);
-            std::vector<int> fill(ncell, 0);
-            for (int s = 0; s < Npad; s++) if (cellOf[s] >= 0) cellAtoms[cellStart[cellOf[s]] + fill[cellOf[s]]++] = s;
-        }
-        std::vector<int> slotOf(Npad, -1);            // sorted j index -> position in this block's candidate list
-        std::vector<std::pair<int, int>> cand;        // (key = sj<<27 | index, code)
-        std::vector<int> tileMask;                    // per tile of the current block: mask index or -1
-        numMaskTiles = 0;
-        for (int I = 0; I < numBlocks; I++) {
-            cand.clear();
-            const double* c = &bc[3 * (size_t)I]; const double* h = &bh[3 * (size_t)I];
-            bool emptyBlock = true;
-            for (int k = 0; k < 32; k++) if (sortedToUser[I * 32 + k] >= 0) emptyBlock = false;
-            if (!emptyBlock) {
-                if (allPairs) {
-                    for (int J = 0; J < numBlocks; J++) {
-                        if (J == I || !owns(I, J)) continue;
-                        for (int k = 0; k < 32; k++) if (sortedToUser[J * 32 + k] >= 0) cand.push_back({J * 32 + k, SNB_JCODE_CENTER});
-                    }
-                } else {
-                    int cmin[3], cmax[3];
-                    for (int d = 0; d < 3; d++) {
-                        cmin[d] = (int)std::floor((c[d] - h[d] - R - lo[d]) / csz[d]);
-                        cmax[d] = (int)std::floor((c[d] + h[d] + R - lo[d]) / csz[d]);
-                        if (!periodic) { cmin[d] = std::max(cmin[d], 0); cmax[d] = std::min(cmax[d], nc[d] - 1); }
-                    }
-                    for (int ix = cmin[0]; ix <= cmax[0]; ix++) for (int iy = cmin[1]; iy <= cmax[1]; iy++) for (int iz = cmin[2]; iz <= cmax[2]; iz++) {
-                        int cc[3] = {ix, iy, iz}, img[3] = {0, 0, 0};
-                        for (int d = 0; d < 3; d++) { img[d] = (int)std::floor((double)cc[d] / nc[d]); cc[d] -= img[d] * nc[d]; }
-                        if (std::abs(img[0]) > 1 || std::abs(img[1]) > 1 || std::abs(img[2]) > 1) continue;
-                        const double sh[3] = {img[0] * box[0], img[1] * box[4], img[2] * box[8]};
-                        const int code = (img[0] + 2) * 25 + (img[1] + 2) * 5 + (img[2] + 2);
-                        const int cell = (cc[0] * nc[1] + cc[1]) * nc[2] + cc[2];
-                        for (int a = cellStart[cell]; a < cellStart[cell + 1]; a++) {
-                            const int sj = cellAtoms[a]; const int J = sj >> 5;
-                            if (J == I || !owns(I, J)) continue;
-                            const int u = sortedToUser[sj];
-                            double d2 = 0;
-                            for (int d = 0; d < 3; d++) { double dd = std::fabs(wp[3 * (size_t)u + d] + sh[d] - c[d]) - h[d]; if (dd > 0) d2 += dd * dd; }
-                            if (d2 < R * R) cand.push_back({sj, code});
-                        }
-                    }
-                }
-            }
-            // group by j subset, ascending index inside a group
-            std::sort(cand.begin(), cand.end(), [&](const std::pair<int, int>& a, const std::pair<int, int>& b) {
-                int sa = blkSubset[a.first >> 5], sb = blkSubset[b.first >> 5];
-                return sa != sb ? sa < sb : a.first < b.first;
-            });
-            const int firstTile = (int)hTileInfo.size();
-            // diagonal tile first
-            tileMask.clear();
-            {
-                for (int k = 0; k < 32; k++) hTileJ.push_back((sortedToUser[I * 32 + k] >= 0) ? ((I * 32 + k) | (SNB_JCODE_CENTER << SNB_JSHIFT_BITS)) : -1);
-                int mi = (int)(hMasks.size() / 32);
-                hMasks.resize(hMasks.size() + 32, 0u);
-                for (int i = 0; i < 32; i++) { unsigned m = 0; for (int j = 0; j <= i; j++) m |= 1u << j; hMasks[(size_t)mi * 32 + i] = m; }   // keep j > i only
-                hTileInfo.push_back(make_int4(blkSubset[I] * (blkSubset[I] + 3) / 2, mi, blkSubset[I], 0));      // (slice, mask, j subset)
-                tileMask.push_back(mi);
-                for (int k = 0; k < 32; k++) slotOf[I * 32 + k] = k;    // slots 0..31 = diagonal tile
-            }
-            size_t pos = 0;
-            while (pos < cand.size()) {
-                const int sjSub = blkSubset[cand[pos].first >> 5];
-                int cnt = 0;
-                const int tIndex = (int)hTileInfo.size() - firstTile;
-                while (pos < cand.size() && cnt < 32 && blkSubset[cand[pos].first >> 5] == sjSub) {
-                    hTileJ.push_back(cand[pos].first | (cand[pos].second << SNB_JSHIFT_BITS));
-                    slotOf[cand[pos].first] = tIndex * 32 + cnt;
-                    cnt++; pos++;
-                }
-                for (; cnt < 32; cnt++) hTileJ.push_back(-1);
-                { const int a = std::max(blkSubset[I], sjSub), b = std::min(blkSubset[I], sjSub); hTileInfo.push_back(make_int4(a * (a + 1) / 2 + b, -1, sjSub, 0)); }
-                tileMask.push_back(-1);
-            }
-            // exclusion masks
-            for (int k = 0; k < 32; k++) {
-                int u = sortedToUser[I * 32 + k]; if (u < 0) continue;
-                for (int e = exStart[u]; e < exStart[u + 1]; e++) {
-                    const int sj = userToSorted[exList[e]];
-                    const int sl = slotOf[sj];
-                    if (sl < 0) continue;
-                    const int t = sl >> 5, bit = sl & 31;
-                    if (tileMask[t] < 0) { tileMask[t] = (int)(hMasks.size() / 32); hMasks.resize(hMasks.size() + 32, 0u); hTileInfo[firstTile + t].y = tileMask[t]; }
-                    hMasks[(size_t)tileMask[t] * 32 + k] |= 1u << bit;
-                }
-            }
-            // padding slots (partially filled tiles, padded i rows) are masked out as well, so that parked padding
-            // coordinates can never contribute (in the per-pair-wrap variant they would be folded back into the box)
-            {
-                unsigned iPadRows = 0;
-                for (int k = 0; k < 32; k++) if (sortedToUser[I * 32 + k] < 0) iPadRows |= 1u << k;
-                for (int t = 0; t < (int)tileMask.size(); t++) {
-                    unsigned jPad = 0;
-                    for (int k = 0; k < 32; k++) if (hTileJ[(size_t)(firstTile + t) * 32 + k] == -1) jPad |= 1u << k;
-                    if (!jPad && !iPadRows) continue;
-                    if (tileMask[t] < 0) { tileMask[t] = (int)(hMasks.size() / 32); hMasks.resize(hMasks.size() + 32, 0u); hTileInfo[firstTile + t].y = tileMask[t]; }
-                    for (int k = 0; k < 32; k++) hMasks[(size_t)tileMask[t] * 32 + k] |= ((iPadRows >> k) & 1u) ? 0xFFFFFFFFu : jPad;
-                }
-            }
-            for (int t = 0; t < (int)tileMask.size(); t++) if (tileMask[t] >= 0) numMaskTiles++;
-            // reset the scratch map
-            for (int k = 0; k < 32; k++) slotOf[I * 32 + k] = -1;
-            for (auto& cd : cand) slotOf[cd.first] = -1;
-            hBlockTiles[I] = make_int2(firstTile, (int)hTileInfo.size() - firstTile);
-            if (emptyBlock) { hBlockTiles[I].y = 0; }
-        }
-        numTiles = (int64_t)hTileInfo.size();
-        // work items: runs of <= 8 tiles of one i-block (fine grain => several rounds of waves per CU, small tail)
-        std::vector<int4> hWork;
-        const int CH = 8;
-        // sharded engines keep the work items of the i-blocks they own (block index % shard_count == shard_rank): a rule every rank
-        // evaluates identically, whatever order its own builder emitted the items in
-        shardTiles = 0;
-        for (int b = 0; b < numBlocks; b++) {
-            if (!ownsBlock(b)) continue;
-            shardTiles += hBlockTiles[b].y;
-            for (int o = 0; o < hBlockTiles[b].y; o += CH) hWork.push_back(make_int4(b, hBlockTiles[b].x + o, std::min(CH, hBlockTiles[b].y - o), blkSubset[b]));
-        }
-        std::stable_sort(hWork.begin(), hWork.end(), [&](const int4& a, const int4& b) { return a.z > b.z; });
-        numWorkItems = (int)hWork.size();
-        // 7. upload
+        static_assert(kJShiftBits == SNB_JSHIFT_BITS && kJCodeCenter == SNB_JCODE_CENTER, "host_lists.h packs the tile entries the kernels unpack");
         posq.upload(hPosq, stream); sigeps.upload(hSigeps, stream); imageOffset.upload(hOff, stream);
-        dSortedToUser.upload(sortedToUser, stream); dUserToSorted.upload(userToSorted, stream);
-        blockSubset.upload(blkSubset, stream); workItems.upload(hWork, stream);
-        tileJ.upload(hTileJ, stream); tileInfo.upload(hTileInfo, stream); masks.upload(hMasks, stream);
-        atomSubset.upload(hAtomSubset, stream); atomGrid.upload(hAtomGrid, stream);
+        dSortedToUser.upload(L.sortedToUser, stream); dUserToSorted.upload(L.userToSorted, stream);
+        blockSubset.upload(L.blockSubset, stream); upload(workItems, L.workItems, stream);
+        tileJ.upload(L.tileJ, stream); upload(tileInfo, L.tileInfo, stream); masks.upload(L.masks, stream);
+        atomSubset.upload(L.atomSubset, stream); atomGrid.upload(L.atomGrid, stream);
+        if (colCells[0] > 0) upload(colRange, L.colRange, stream);
         layoutForces();
         HIPCHECK(hipStreamSynchronize(stream));
         needRebuild = false; paramsDirty = false; stepsSinceRebuild = 0;
@@ -1013,7 +764,7 @@ public:
     }
 
     // Static (sort-independent) device data: 1-4 list and exclusion CSR in USER indices (Q6:
-    // ReferenceNonbondedSlicingKernels.cpp:99-112, 129-131), per-atom parameters in user order, the padded subset layout.
+    // ReferenceNonbondedSlicingKernels.cpp:99-112, 129-131), per-atom parameters in user order, the grid slot of every subset.
     // 1-4 list in user order: the exceptions with non-zero base parameters, or flagged by the caller, or carrying a parameter offset (Q6).
     // Structure only (pairs, slices, base values, offsets in CSR per 1-4 entry); the values are formed on the device (syncParameters).
     void upload14() {
@@ -1092,35 +843,22 @@ public:
 
     void uploadStatic() {
         const size_t m = excPairs.size() / 2;
-        std::vector<int> hStart((size_t)N + 1, 0), hList(2 * m);
+        hExclStart.assign((size_t)N + 1, 0); hExclList.resize(2 * m);
         for (size_t k = 0; k < m; k++) {
             const int a = excPairs[2 * k], b = excPairs[2 * k + 1];
-            hStart[a + 1]++; hStart[b + 1]++;
+            hExclStart[a + 1]++; hExclStart[b + 1]++;
         }
-        for (int i = 0; i < N; i++) hStart[i + 1] += hStart[i];
-        { std::vector<int> fill(N, 0); for (size_t k = 0; k < m; k++) { const int a = excPairs[2 * k], b = excPairs[2 * k + 1]; hList[hStart[a] + fill[a]++] = b; hList[hStart[b] + fill[b]++] = a; } }
-        exclStart.upload(hStart, stream); exclList.upload(hList, stream);
+        for (int i = 0; i < N; i++) hExclStart[i + 1] += hExclStart[i];
+        { std::vector<int> fill(N, 0); for (size_t k = 0; k < m; k++) { const int a = excPairs[2 * k], b = excPairs[2 * k + 1]; hExclList[hExclStart[a] + fill[a]++] = b; hExclList[hExclStart[b] + fill[b]++] = a; } }
+        exclStart.upload(hExclStart, stream); exclList.upload(hExclList, stream);
         // user-order parameters: formed on the device from base values, offsets and global parameters
         dUSubset.upload(std::vector<int>(subset.begin(), subset.end()), stream);
         HIPCHECK(hipStreamSynchronize(stream));
         basePDirty = baseEDirty = true;
         syncParameters(true, true);
-        // padded subset layout (depends on subset populations only)
-        std::vector<int> cnt(nsub, 0);
-        for (int i = 0; i < N; i++) cnt[subset[i]]++;
-        hSubsetStart.assign(nsub + 1, 0); hSubsetPaddedStart.assign(nsub + 1, 0);
-        for (int k = 0; k < nsub; k++) { hSubsetStart[k + 1] = hSubsetStart[k] + cnt[k]; hSubsetPaddedStart[k + 1] = hSubsetPaddedStart[k] + ((cnt[k] + 31) / 32) * 32; }
-        staticNpad = hSubsetPaddedStart[nsub];
-        std::vector<unsigned char> pad(std::max(staticNpad, 1), 0);
-        staticBlkSubset.clear();
-        for (int k = 0; k < nsub; k++) {
-            for (int x = hSubsetPaddedStart[k] + cnt[k]; x < hSubsetPaddedStart[k + 1]; x++) pad[x] = 1;
-            for (int bb = hSubsetPaddedStart[k] / 32; bb < hSubsetPaddedStart[k + 1] / 32; bb++) staticBlkSubset.push_back(k);
-        }
-        dSubsetStart.upload(hSubsetStart, stream); dSubsetPaddedStart.upload(hSubsetPaddedStart, stream); dPadFlag.upload(pad, stream);
-        std::vector<int> slot(nsub, -1);
-        if (cfg.shard_count == 1) std::iota(slot.begin(), slot.end(), 0); else for (size_t g = 0; g < ownedSubsets.size(); g++) slot[ownedSubsets[g]] = (int)g;
-        dSlotOfSubset.upload(slot, stream);
+        hSlotOfSubset.assign(nsub, -1);
+        if (cfg.shard_count == 1) std::iota(hSlotOfSubset.begin(), hSlotOfSubset.end(), 0); else for (size_t g = 0; g < ownedSubsets.size(); g++) hSlotOfSubset[ownedSubsets[g]] = (int)g;
+        dSlotOfSubset.upload(hSlotOfSubset, stream);
         HIPCHECK(hipStreamSynchronize(stream));
         staticDirty = false;
         npadPredict = 0;      // (subsets or exclusions may have changed: the next rebuild waits for its padded count again)
@@ -1281,23 +1019,12 @@ public:
             cell[1] = cell[2] = cell[3] = cell[5] = cell[6] = cell[7] = 0;
         }
         const double* box = cell;      // (shadows the member for the rest of the build)
-        const double volume = box[0] * box[4] * box[8];
-        const double aTarget = std::cbrt(32.0 * volume / std::max(N, 1));
-        for (int d = 0; d < 3; d++) if (!(4.0 * aTarget + 2 * R < box[4 * d])) return false;   // tile-image scheme needs extent + 2R < L (checked exactly on the GPU too)
+        const double diag[3] = {box[0], box[4], box[8]}; const int mesh[3] = {pme.d.nx, pme.d.ny, pme.d.nz}, noMesh[3] = {0, 0, 0};
+        const SortColumns sc = sortColumns(N, diag, (isPme() && nGrids > 0) ? mesh : noMesh);
+        for (int d = 0; d < 3; d++) if (!(4.0 * sc.aTarget + 2 * R < box[4 * d])) return false;   // tile-image scheme needs extent + 2R < L (checked exactly on the GPU too)
         auto t0 = std::chrono::steady_clock::now();
-        int ncx = std::max(1, std::min(2048, (int)std::lround(box[0] / aTarget)));
-        int ncy = std::max(1, std::min(2048, (int)std::lround(box[4] / aTarget)));
-        colCells[0] = colCells[1] = 0;
-        if (isPme() && nGrids > 0) {
-            auto pick = [&](int n, double L) {
-                int best = 0; double bestErr = 1e300;
-                for (int d = 5; d <= 16 && d <= n; d++) if (n % d == 0) { double er = std::fabs(d * L / n - aTarget); if (er < bestErr) { bestErr = er; best = d; } }
-                return best;
-            };
-            const int px = pick(pme.d.nx, box[0]), py = pick(pme.d.ny, box[4]);
-            if (px > 0 && py > 0 && sizeof(double) * (size_t)px * py * pme.d.nz <= 60 * 1024 && std::max(pme.d.nx, std::max(pme.d.ny, pme.d.nz)) < 1024) {      // (the packed mesh cell of an atom holds 10 bits per axis)
-            colCells[0] = px; colCells[1] = py; ncx = pme.d.nx / px; ncy = pme.d.ny / py; }
-        }
+        const int ncx = sc.ncx, ncy = sc.ncy;
+        colCells[0] = sc.colCells[0]; colCells[1] = sc.colCells[1];
         // phase A: sort and block segmentation (the padded atom count depends on where the sorted order jumps)
         dUserToSorted.resize(N);
         colRange.resize((size_t)nsub * ncx * ncy); dZIndex.resize((size_t)nsub * ncx * ncy * 65);
