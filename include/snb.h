@@ -314,6 +314,32 @@ snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out);   /* cumulat
 snb_status snb_evaluate_atom_energies(snb_handle h, int32_t include_direct, int32_t include_reciprocal,
                                       double* atom_energies /* [n_atoms][n_subsets][2], USER order */, int32_t out_is_device);
 
+/* -- per-atom forces by subset and term -------------------------------------------------------- */
+/* The force split by partner subset: atom_forces[i][J][t][d] = G[i][J][t] = - d E_raw[slice(s_i, J)][t] / d r_i, component d, in kJ/mol/nm
+ * (t = 0 Coulomb, 1 vdW; s_i the subset of atom i): the force ALL atoms of subset J put on atom i, for every atom and every subset in one
+ * evaluation.  It is raw: not scaled by the lambdas and independent of them.  E_raw is linear in the lambdas, so the force on atom i at
+ * ANY lambda state is  sum_J sum_t lambda[slice(s_i, J)][t] G[i][J][t]  -- the forces of another state without another evaluation, the
+ * lambda-derivative of the forces as the sum of the bound columns, the mean force the solvent puts on a ligand atom as one column.
+ * Attributed: pairs inside the cutoff (both ends, diagonal tiles included), the Ewald exclusion corrections (into t = 0; the LJPME
+ * dispersion part into t = 1), the 1-4 exceptions (both ends), the reciprocal part from the UNMIXED potentials of the subsets' meshes,
+ * -q_i grad psi_J(r_i) into t = 0 (LJPME: -c6_i grad psi_J of the dispersion mesh into t = 1).  The Ewald self term, the neutralising
+ * background and the long-range dispersion correction carry no force: nothing is added for them.  Parameters are the effective ones (base
+ * values + offsets at the current global parameters).  USER atom order; host or device by out_is_device.
+ * The call behaves as an energy-only step behaves: it takes the current box and positions (with a bound context, posq through the same
+ * gather), follows the neighbour-list rules of any execute (a due rebuild happens, a pending side build is finished or cancelled as for an
+ * energy-only step; the forces of the last forces step are kept across a rebuild it performs), runs as plain launches -- it never captures
+ * or updates a step graph -- and counts in no timer sum and not in n_timed.
+ * It writes ONLY the table: the forces (snb_get_forces), the buffer of snb_set_force_output, a binding's force_buffer / energy_buffer /
+ * deriv_buffer and the engine's slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) stay bit for bit what they were.
+ * Host output returns after one synchronisation; device output is complete in stream order on snb_config.stream.
+ * Everything is checked before anything is enqueued: atom_forces NULL or both include flags 0: SNB_ERR_INVALID_ARGUMENT; shard_count > 1:
+ * SNB_ERR_UNSUPPORTED; SNB_Ewald with include_reciprocal (the k-sum of classic Ewald is not attributed; direct-only works):
+ * SNB_ERR_UNSUPPORTED; particles, box or positions missing: what snb_execute returns in that state.  The working memory (a table over the
+ * sorted atoms) is allocated at the first call: an engine that never calls pays nothing.  The table's double sums are accumulated with
+ * atomics: equal from call to call up to the rounding of the sums, not bit for bit, in every precision mode. */
+snb_status snb_evaluate_atom_forces(snb_handle h, int32_t include_direct, int32_t include_reciprocal,
+                                    double* atom_forces /* [n_atoms][n_subsets][2][3], USER order */, int32_t out_is_device);
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

@@ -20,6 +20,7 @@ SYMBOLS = [
     "snb_rebuild_neighbors", "snb_execute", "snb_get_forces", "snb_set_force_output", "snb_set_shard_blocks", "snb_get_slice_energies", "snb_slice_energies_device", "snb_synchronize",
     "snb_get_pme_parameters", "snb_get_ljpme_parameters", "snb_get_stats", "snb_reset_timers", "snb_set_timing_interval", "snb_legal_grid_size", "snb_abi_version",
     "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed", "snb_evaluate_frames", "snb_get_frame_stats", "snb_evaluate_atom_energies",
+    "snb_evaluate_atom_forces",
 ]
 
 SNB_OK, SNB_ERR_INVALID_ARGUMENT, SNB_ERR_HIP, SNB_ERR_BOX_TOO_SMALL, SNB_ERR_NOT_PME, SNB_ERR_STATE, SNB_ERR_UNSUPPORTED = range(7)
@@ -132,6 +133,7 @@ def lib():
     L.snb_evaluate_frames.argtypes = [vp, ctypes.POINTER(SnbFrameBatch)]
     L.snb_get_frame_stats.argtypes = [vp, ctypes.POINTER(SnbFrameStats)]
     L.snb_evaluate_atom_energies.argtypes = [vp, i32, i32, vp, i32]      # (the table as an address: host or device by out_is_device)
+    L.snb_evaluate_atom_forces.argtypes = [vp, i32, i32, vp, i32]        # (the same)
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError if the header and the library ever diverge
     _lib = L

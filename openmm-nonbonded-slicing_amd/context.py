@@ -357,6 +357,39 @@ class HipCalcSlicedNonbondedForceKernel:
             out[g] = table[np.asarray(list(atoms), dtype=np.int64)].sum(axis=0)
         return out
 
+    def computeAtomForces(self, context, includeDirect=True, includeReciprocal=True, devicePointer=None):
+        """Per-atom forces by partner subset and term (include/snb.h, snb_evaluate_atom_forces): ``G[i][J][t] = -dE_raw[slice(s_i, J)][t]/dr_i``,
+        the (Coulomb, vdW) force all atoms of subset J put on atom i at the context's positions, box and parameters, in one evaluation --
+        the mean force of the solvent on a ligand atom, force-matching targets, the forces at any lambda state (forcesFromAtomForces).
+        Returns an ndarray (N, n_subsets, 2, 3) in user atom order, kJ/mol/nm, or None when ``devicePointer`` (address of a double
+        [N][n_subsets][2][3] array on the engine's device, complete in stream order) takes the table.  Not scaled by the lambdas.  Forces,
+        force outputs and the slice energies of the last steps stay as they are."""
+        self._push_state(context)
+        if devicePointer is not None:
+            self._check(self._lib.snb_evaluate_atom_forces(self._h, int(bool(includeDirect)), int(bool(includeReciprocal)), ctypes.c_void_p(int(devicePointer)), 1))
+            return None
+        out = np.zeros((self.numParticles, self.numSubsets, 2, 3))
+        self._check(self._lib.snb_evaluate_atom_forces(self._h, int(bool(includeDirect)), int(bool(includeReciprocal)), out.ctypes.data_as(ctypes.c_void_p), 0))
+        return out
+
+    @staticmethod
+    def forcesFromAtomForces(table, subsets, lambdas):
+        """The forces (N, 3) a per-atom force table implies at a lambda state: F_i = sum_J sum_t lambdas[slice(s_i, J)][t] G[i][J][t], with
+        ``lambdas`` the (S, 2) table of (Coulomb, vdW) scaling factors per slice."""
+        table = np.asarray(table, dtype=np.float64); subsets = np.asarray(subsets); lambdas = np.asarray(lambdas, dtype=np.float64)
+        n = table.shape[1]
+        out = np.zeros((table.shape[0], 3))
+        for i in range(n):
+            rows = subsets == i
+            for j in range(n):
+                out[rows] += np.einsum("t,ntd->nd", lambdas[sliceIndex(i, j)], table[rows, j])
+        return out
+
+    @staticmethod
+    def groupAtomForces(table, groups):
+        """Sums of a per-atom force table over lists of atom indices, one list per group (residue, molecule): (G, n_subsets, 2, 3)."""
+        return HipCalcSlicedNonbondedForceKernel.groupAtomEnergies(table, groups)      # (the reduction does not depend on the entry's shape)
+
     def computeSliceEnergiesForFrames(self, context, positions=None, boxes=None, slices=None, lambdaStates=None, positionsDevicePointer=None, numFrames=None):
         """Raw per-slice energies [F][S][2] of F stored frames in one call (include/snb.h, snb_evaluate_frames): the loop of an MBAR or
         reweighting pass over a trajectory, pipelined inside the engine -- the list of the next frame is built beside the step of this one.
@@ -518,6 +551,9 @@ class SlicedNonbondedForceImpl:
     def getAtomEnergies(self, context, **options):
         return self.kernel.computeAtomEnergies(context, **options)
 
+    def getAtomForces(self, context, **options):
+        return self.kernel.computeAtomForces(context, **options)
+
 
 class System:
     def __init__(self):
@@ -613,6 +649,15 @@ class Context:
         for impl in self._impls:
             if impl.owner is force:
                 return impl.getAtomEnergies(self, **options)
+        raise OpenMMException("force not in this context")
+
+    def getAtomForces(self, force, **options):
+        """Per-atom forces of ``force`` by partner subset and term, (N, n_subsets, 2, 3): HipCalcSlicedNonbondedForceKernel.computeAtomForces."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        for impl in self._impls:
+            if impl.owner is force:
+                return impl.getAtomForces(self, **options)
         raise OpenMMException("force not in this context")
 
     def _updateParametersInContext(self, force):

@@ -113,6 +113,7 @@ struct EngineBase {
     virtual void getPme(double*, int32_t*, bool dispersion) = 0;
     virtual void evaluateFrames(const snb_frame_batch*) = 0;
     virtual void evaluateAtomEnergies(int, int, double*, int) = 0;
+    virtual void evaluateAtomForces(int, int, double*, int) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
@@ -1925,6 +1926,73 @@ public:
         }
     }
 
+    // ------------------------------------------------------------------------------------------
+    // Per-atom forces by partner subset and term (snb_evaluate_atom_forces): G[i][J][t] = -dE_raw[slice(s_i, J)][t]/dr_i.
+    // The frame, the refusals and the paths of evaluateAtomEnergies above, with the kernels of atomforce.hip: pair forces with every lambda 1
+    // into both ends' columns, the derivative part of the interpolation per (atom, held mesh) of the unmixed pipeline, no closed-form term
+    // (none carries a force).  Writes only its table; working and staging tables are its own.
+    // ------------------------------------------------------------------------------------------
+    DevBuf<double> atomFTab, atomFOut;      // sorted-order working table [Npad][nsub][2][3]; user-order staging of a host result (both allocated at the first call)
+    void evaluateAtomForces(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
+        if (!out) { err = "snb_evaluate_atom_forces: atom_forces is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (!includeDirect && !includeRecip) { err = "snb_evaluate_atom_forces: neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (cfg.shard_count > 1) { err = "snb_evaluate_atom_forces: not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        if (cfg.method == SNB_Ewald && includeRecip) { err = "snb_evaluate_atom_forces: the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        beginExecute(false, includeRecip);
+        const size_t tabN = (size_t)Npad * nsub * 6, outN = (size_t)N * nsub * 6;
+        atomFTab.resize(tabN);
+        if (!outIsDevice) atomFOut.resize(outN);
+        double* const dst = outIsDevice ? out : atomFOut.p;
+        launchZeroFill(atomFTab.p, sizeof(double) * tabN, stream);
+        // the position-gather pass of a step that clears nothing: sorted positions, the Coulomb-mesh cells, the displacement watch
+        const bool recip = includeRecip && isPme() && nGrids > 0;
+        GatherCells<Real> gc;
+        std::memset(&gc, 0, sizeof(gc));
+        cellsFromGather = false; traceThisStep = false;
+        if (recip) {
+            PmeParams<Real> pp;
+            std::memset(&pp, 0, sizeof(pp));
+            fillPme(pp, pme, false);
+            if (pp.sortNcx > 0 && pp.colRange != nullptr) {
+                for (int i = 0; i < 9; i++) { gc.recip[i] = pp.recip[i]; gc.recipLo[i] = pp.recipLo[i]; }
+                gc.nx = pp.d.nx; gc.ny = pp.d.ny; gc.nz = pp.d.nz; gc.cells = pp.cells; gc.atomGrid = pp.atomGrid;
+                cellsFromGather = true;
+            }
+            if (dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
+        }
+        if (cfg.neighbor_padding > 0 && posRef.p) {
+            gc.posRef = posRef.p; gc.flags = dDispFlags;
+            const double half = 0.5 * cfg.neighbor_padding;
+            gc.fail2 = (Real)(half * half); gc.warn2 = (Real)(0.64 * half * half);
+        }
+        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream); }
+        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream);
+        if (includeDirect) {
+            DirectParams<Real> p; PairListParams<Real> q;
+            std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
+            fillDirect(p); fillPairLists(q);
+            launchAtomForcePairs<Real>(p, methodClass(), wrapMode, &q, atomFTab.p, stream);
+        }
+        if (recip) {
+            PmeParams<Real> pp;
+            std::memset(&pp, 0, sizeof(pp));
+            fillPme(pp, pme, false); pp.mix = 0;
+            runPmeFront(pp, stream);
+            launchAtomField<Real>(pp, atomFTab.p, stream);
+            if (cfg.method == SNB_LJPME) {
+                fillPme(pp, dpme, false); pp.mix = 0;
+                runPmeFront(pp, stream);
+                launchAtomField<Real>(pp, atomFTab.p, stream);
+            }
+        }
+        launchAtomForceFinish(atomFTab.p, dUserToSorted.p, N, nsub, dst, stream);
+        endExecute();
+        if (!outIsDevice) {
+            HIPCHECK(hipMemcpyAsync(out, atomFOut.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+        }
+    }
+
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
     void runEwald(bool energy, bool forces) {
         if (hKvec.empty()) {
@@ -2164,6 +2232,9 @@ snb_status snb_evaluate_frames(snb_handle h, const snb_frame_batch* b) {
 }
 snb_status snb_evaluate_atom_energies(snb_handle h, int32_t includeDirect, int32_t includeRecip, double* atomEnergies, int32_t outIsDevice) {
     return guard(h, [&] { h->impl->evaluateAtomEnergies(includeDirect, includeRecip, atomEnergies, outIsDevice); });
+}
+snb_status snb_evaluate_atom_forces(snb_handle h, int32_t includeDirect, int32_t includeRecip, double* atomForces, int32_t outIsDevice) {
+    return guard(h, [&] { h->impl->evaluateAtomForces(includeDirect, includeRecip, atomForces, outIsDevice); });
 }
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 

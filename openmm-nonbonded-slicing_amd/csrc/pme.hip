@@ -61,37 +61,7 @@ template <typename Real, int R1 = 0, int R2 = 0>
 __device__ inline Cx<Real>* fftLines(Cx<Real>* a, Cx<Real>* b, int n, const int* factors, int nf, int sign, const Cx<Real>* tw, int nb, int BS, int tid, int nthreads);
 template <typename Real> __device__ inline Cx<Real> cmul(Cx<Real> a, Cx<Real> b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
-// ---------------------------------------------------------------------------------------------------
-// B-splines of order 5 and their derivatives (ReferencePME.cpp:264-317), in registers.
-// ---------------------------------------------------------------------------------------------------
-template <typename Real> __device__ inline void bspline5(Real dr, Real* d, Real* dd) {
-    d[4] = 0; d[1] = dr; d[0] = 1 - dr; d[2] = 0; d[3] = 0;
-    // k = 3
-    {
-        const Real div = Real(0.5);
-        d[2] = div * dr * d[1];
-        d[1] = div * ((dr + 1) * d[0] + (2 - dr) * d[1]);
-        d[0] = div * (1 - dr) * d[0];
-    }
-    // k = 4
-    {
-        const Real div = Real(1.0 / 3.0);
-        d[3] = div * dr * d[2];
-        d[2] = div * ((dr + 1) * d[1] + (3 - dr) * d[2]);
-        d[1] = div * ((dr + 2) * d[0] + (2 - dr) * d[1]);
-        d[0] = div * (1 - dr) * d[0];
-    }
-    dd[0] = -d[0];
-    dd[1] = d[0] - d[1]; dd[2] = d[1] - d[2]; dd[3] = d[2] - d[3]; dd[4] = d[3] - d[4];
-    {
-        const Real div = Real(0.25);
-        d[4] = div * dr * d[3];
-        d[3] = div * ((dr + 1) * d[2] + (4 - dr) * d[3]);
-        d[2] = div * ((dr + 2) * d[1] + (3 - dr) * d[2]);
-        d[1] = div * ((dr + 3) * d[0] + (2 - dr) * d[1]);
-        d[0] = div * (1 - dr) * d[0];
-    }
-}
+// (bspline5: B-splines of order 5 and their derivatives, snb_internal.h -- shared with the per-atom field kernel of atomforce.hip)
 
 // grid index + fraction (ReferencePME.cpp:245-254)
 template <typename Real> __device__ inline Real pmeCharge(const PmeParams<Real>& p, int atom) {

@@ -322,6 +322,10 @@ template <typename Real> void launchAtomPairs(const DirectParams<Real>& p, int m
 template <typename Real> void launchAtomPotential(const PmeParams<Real>& p, double* tab, hipStream_t s);   // + q_i psi_J(r_i) from the unmixed real-space potentials of p
 template <typename Real> void launchAtomFinish(const double* tab, const int* userToSorted, const int* blockSubset, const typename Vec<Real>::T4* posq, const typename Vec<Real>::T2* sigeps,
                                                int nAtoms, int nsub, const SliceFinish& f, double* out, hipStream_t s);   // closed-form terms, sorted -> user order: out[nAtoms][nsub][2]
+// per-atom forces by subset and term (atomforce.hip, snb_evaluate_atom_forces): tab = double [Npad][nsub][2][3] over the sorted index, added to
+template <typename Real> void launchAtomForcePairs(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, double* tab, hipStream_t s);
+template <typename Real> void launchAtomField(const PmeParams<Real>& p, double* tab, hipStream_t s);   // - q_i grad psi_J(r_i) from the unmixed real-space potentials of p
+void launchAtomForceFinish(const double* tab, const int* userToSorted, int nAtoms, int nsub, double* out, hipStream_t s);   // sorted -> user order: out[nAtoms][nsub][2][3]
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s);   // 1: forward z FFT already done; 2: ... and the spectrum is plane-major (plane path)
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s);   // rebuild time: fills the plane path's kernel-value table
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s);   // after a spreader that returned 2: k_planeXY + k_fftZInvMix instead of forward FFT, convolution, inverse FFT
@@ -367,6 +371,39 @@ template <typename Real> __device__ inline void gridCoord(const Real* recip, con
             frac[d] = t - ti;
             idx[d] = ti >= n[d] ? ti - n[d] : ti;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// B-splines of order 5 and their derivatives (ReferencePME.cpp:264-317), in registers.  Shared by the PME kernels (pme.hip)
+// and the per-atom field kernel (atomforce.hip).
+// ---------------------------------------------------------------------------------------------------
+template <typename Real> __device__ inline void bspline5(Real dr, Real* d, Real* dd) {
+    d[4] = 0; d[1] = dr; d[0] = 1 - dr; d[2] = 0; d[3] = 0;
+    // k = 3
+    {
+        const Real div = Real(0.5);
+        d[2] = div * dr * d[1];
+        d[1] = div * ((dr + 1) * d[0] + (2 - dr) * d[1]);
+        d[0] = div * (1 - dr) * d[0];
+    }
+    // k = 4
+    {
+        const Real div = Real(1.0 / 3.0);
+        d[3] = div * dr * d[2];
+        d[2] = div * ((dr + 1) * d[1] + (3 - dr) * d[2]);
+        d[1] = div * ((dr + 2) * d[0] + (2 - dr) * d[1]);
+        d[0] = div * (1 - dr) * d[0];
+    }
+    dd[0] = -d[0];
+    dd[1] = d[0] - d[1]; dd[2] = d[1] - d[2]; dd[3] = d[2] - d[3]; dd[4] = d[3] - d[4];
+    {
+        const Real div = Real(0.25);
+        d[4] = div * dr * d[3];
+        d[3] = div * ((dr + 1) * d[2] + (4 - dr) * d[3]);
+        d[2] = div * ((dr + 2) * d[1] + (3 - dr) * d[2]);
+        d[1] = div * ((dr + 3) * d[0] + (2 - dr) * d[1]);
+        d[0] = div * (1 - dr) * d[0];
     }
 }
 
