@@ -1265,8 +1265,12 @@ public:
         // (the sort columns are cut on the Coulomb mesh, `pme`, for every mesh; the mesh size and the bricks are this plan's)
         fprintf(stderr, "[snb] %s mesh %d x %d x %d: sort columns %d x %d of %d x %d cells, %s", name, plan.d.nx, plan.d.ny, plan.d.nz,
                 colCells[0] > 0 ? pme.d.nx / colCells[0] : 0, colCells[0] > 0 ? pme.d.ny / colCells[1] : 0, colCells[0], colCells[1],
-                !bricks ? "atomic spreader\n" : "");
-        if (bricks) fprintf(stderr, "bricks of %d x %d columns, %s (slabs %d, margin %d)\n", gx, gy, plan.ownSlabs > 0 ? "own-atoms spreader planned" : "scanning brick spreader", plan.ownSlabs, plan.ownMargin);
+                !bricks ? "atomic spreader" : "");
+        if (bricks) fprintf(stderr, "bricks of %d x %d columns, %s (slabs %d, margin %d)", gx, gy, plan.ownSlabs > 0 ? "own-atoms spreader planned" : "scanning brick spreader", plan.ownSlabs, plan.ownMargin);
+        // the (R1, R2) instantiations the mesh size selects (0 * 0: the staged transforms; plane splits 0 * 0: no plane kernel for this size)
+        const PmePlanDims& d = plan.d;
+        fprintf(stderr, "; fft splits x %d*%d y %d*%d z %d*%d, plane splits x %d*%d y %d*%d (%s)\n", d.rx1, d.rx2, d.ry1, d.ry2, d.rz1, d.rz2, d.px1, d.px2, d.py1, d.py2,
+                (d.px1 <= 0 || d.py1 <= 0) ? "none" : planeIsStatic(d) ? "static" : "run-time");
     }
     void planOwnSpread(PmePlan<Real>& plan) {
         plan.ownSlabs = 0;

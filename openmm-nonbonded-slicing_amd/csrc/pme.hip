@@ -1743,6 +1743,7 @@ static bool planeSquare(const PmePlanDims& d) {
 #undef X
     return false;
 }
+bool planeIsStatic(const PmePlanDims& d) { return planeSquare(d); }
 template <typename Real> static size_t planeLds(const PmeParams<Real>& p) { return sizeof(Cx<Real>) * ((size_t)p.d.nx * (p.d.ny | 1) + p.d.nx + (planeSquare(p.d) ? 0 : p.d.ny)); }
 template <typename Real> static bool planePathOK(const PmeParams<Real>& p) {
     if (switches().noPlaneFft || !std::is_same<Real, float>::value || !p.planeB || !p.planeEterm) return false;

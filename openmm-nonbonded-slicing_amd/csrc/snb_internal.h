@@ -453,5 +453,6 @@ int legalGridSize(int n);
 bool factorize(int n, int* factors, int* nfactors);
 bool splitTwoPass(int n, int* r1, int* r2);
 bool splitPlane(int n, int* r1, int* r2);
+bool planeIsStatic(const PmePlanDims& d);      // a square plane whose split has a plane kernel of its own (pme.hip planeSquare)
 
 }  // namespace snb
