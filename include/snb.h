@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SNB_ABI_VERSION 7
+#define SNB_ABI_VERSION 8
 
 typedef struct snb_engine* snb_handle;
 
@@ -116,7 +116,14 @@ typedef struct {
     int64_t n_kernel_timed[16];
     int64_t n_spread_strays;    /* atoms of the LAST execute whose spreading footprint had left their work-group's LDS region (drift beyond the
                                  * margin since the last re-sort): handled one by one, exactly, by the merge kernel -- normally 0 */
+    /* (ABI 8) the polynomials the pair kernels of this engine use for the direct-space Ewald terms: bit 0 the Coulomb force factor, bit 1
+     * the Coulomb pair energy (single and mixed precision), bit 2 the LJPME dispersion force factor (double precision).  A polynomial
+     * whose residual at this engine's alpha, cutoff and neighbor_padding is too large is replaced by the erfc / exp form. */
+    int64_t ewald_poly_mask;
 } snb_stats;
+#define SNB_POLY_MASK_FORCE 1
+#define SNB_POLY_MASK_ENERGY 2
+#define SNB_POLY_MASK_DISPERSION 4
 #define SNB_K_GATHER 0
 #define SNB_K_SPREAD 1
 #define SNB_K_FFT_Z_FWD 2

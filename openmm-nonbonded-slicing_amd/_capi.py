@@ -11,7 +11,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SNB_LIB_PATH") or os.path.join(_HERE, "libsnb_hip.so")      # (SNB_LIB_PATH: an experimental build of the same ABI, tools/ only)
-SNB_ABI_VERSION = 7
+SNB_ABI_VERSION = 8
 
 # every symbol include/snb.h declares (tests check the library exports each one)
 SYMBOLS = [
@@ -45,6 +45,7 @@ class SnbStats(ctypes.Structure):
         ("last_total_ms", ctypes.c_double), ("last_rebuild_ms", ctypes.c_double), ("sum_direct_ms", ctypes.c_double),
         ("sum_recip_ms", ctypes.c_double), ("sum_total_ms", ctypes.c_double), ("n_timed", ctypes.c_int64), ("n_host_rebuilds", ctypes.c_int64), ("n_list_overruns", ctypes.c_int64),
         ("sum_kernel_ms", ctypes.c_double * 16), ("n_kernel_timed", ctypes.c_int64 * 16), ("n_spread_strays", ctypes.c_int64),
+        ("ewald_poly_mask", ctypes.c_int64),
     ]
 
 

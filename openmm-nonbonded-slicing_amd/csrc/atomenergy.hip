@@ -51,7 +51,7 @@ __device__ __forceinline__ bool pairEnergies(const DirectParams<Real>& p, const 
         }
     }
     const Real qq = qi * xj.w;
-    if ((MC == MC_EWALD || MC == MC_LJPME) && sizeof(Real) == 4 && p.ewUsePoly) {
+    if ((MC == MC_EWALD || MC == MC_LJPME) && sizeof(Real) == 4 && (p.ewUsePoly & SNB_POLY_ENERGY)) {
         // single precision: qq (1/r - Et(r^2)), Et = erf(ar)/r as the degree-13 polynomial of the packed energy kernels -- the error of the
         // Abramowitz & Stegun erfc is one-signed and an atom's column sums thousands of pairs whose direct and reciprocal parts cancel
         const Real t = r2 * p.ewScale - Real(1);

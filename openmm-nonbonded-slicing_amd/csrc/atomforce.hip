@@ -21,7 +21,7 @@ namespace snb {
 
 // Force factors of the pair (i, j), every lambda 1, as the forces instantiation of tileSteps (direct.hip) forms them: the force on i is
 // fC * delta (Coulomb) + fLJ * delta (vdW), delta = r_i - r_j (returned in dx, dy, dz).  Double precision takes the Ewald and dispersion
-// factors from the polynomials of the forces kernels, single precision from erfcFromExp / fexp.  Returns whether the pair is inside the cutoff.
+// factors from the polynomials of the forces kernels where the guard keeps them (p.ewUsePoly), else and in single precision from erfcFromExp / fexp.  Returns whether the pair is inside the cutoff.
 template <typename Real, int MC, bool WRAP>
 __device__ __forceinline__ bool pairForces(const DirectParams<Real>& p, const typename Vec<Real>::T4 pi, const typename Vec<Real>::T2 sei, const Real qi, const Real c6i,
                                            const typename Vec<Real>::T4 xj, const typename Vec<Real>::T2 sj2, Real& dx, Real& dy, Real& dz, Real& fC, Real& fLJ) {
@@ -37,7 +37,7 @@ __device__ __forceinline__ bool pairForces(const DirectParams<Real>& p, const ty
     const Real s6 = s2 * s2 * s2;
     const Real es6 = sei.y * sj2.y * s6;
     fLJ = es6 * (Real(12) * s6 - Real(6));
-    if (MC == MC_LJPME && std::is_same<Real, double>::value) {
+    if (MC == MC_LJPME && std::is_same<Real, double>::value && (p.ewUsePoly & SNB_POLY_DISPERSION)) {
         const Real t = r2 * p.ewScale - Real(1);
         Real gd = p.dispPoly[SNB_DISP_DEG_F64];
 #pragma unroll
@@ -62,7 +62,7 @@ __device__ __forceinline__ bool pairForces(const DirectParams<Real>& p, const ty
         }
     }
     const Real qq = qi * xj.w;
-    if ((MC == MC_EWALD || MC == MC_LJPME) && std::is_same<Real, double>::value) {
+    if ((MC == MC_EWALD || MC == MC_LJPME) && std::is_same<Real, double>::value && (p.ewUsePoly & SNB_POLY_FORCE)) {
         const Real t = r2 * p.ewScale - Real(1);
         Real bt = p.ewPoly[SNB_EW_DEG_F64];
 #pragma unroll

@@ -122,7 +122,9 @@ __device__ inline double rowRor1(double v) {
 // SWITCH: LJ switching function active.  Both are wave-uniform and resolved at compile time so that the common
 // case (no mask, no switch) carries no test for them in the loop.
 // FORCES == false (energy-only tile kernel, ENERGY == true): the energies alone -- no force accumulation, so the force arithmetic is dead code.
-template <typename Real, int MC, bool WRAP, bool ENERGY, bool MASKED, bool SWITCH, bool FORCES = true>
+// POLYALL (double precision): every polynomial of the forces arithmetic passed the guard of ewald_fit.h, so none is tested in the loop; false: each is
+// tested by a wave-uniform branch on the kernel argument (measured on c3 in double: the tests alone cost 18 % of the step, so the common case is compiled without them).
+template <typename Real, int MC, bool WRAP, bool ENERGY, bool MASKED, bool SWITCH, bool FORCES = true, bool POLYALL = false>
 __device__ __forceinline__ void tileSteps(const DirectParams<Real>& p, const typename Vec<Real>::T4* rdPos, const typename Vec<Real>::T2* rdSe,
                                           const typename Vec<Real>::T4 pi, const typename Vec<Real>::T2 sei, const Real qi, const Real qiS, const Real epsiS,
                                           const Real c6i, const Real lamC, const Real lamL, const unsigned maskWord, const int c,
@@ -154,10 +156,10 @@ __device__ __forceinline__ void tileSteps(const DirectParams<Real>& p, const typ
                 const Real es6 = epsiS * sj2.y * s6;
                 fLJ = es6 * (Real(12) * s6 - Real(6));
             }
-            if (MC == MC_LJPME && !ENERGY && std::is_same<Real, double>::value) {
+            if (MC == MC_LJPME && !ENERGY && std::is_same<Real, double>::value && (POLYALL || (p.ewUsePoly & SNB_POLY_DISPERSION))) {
                 // forces only, double: 6 c6 [1 - e^{-x}(1 + x + x^2/2 + x^3/6)] / r^6 = 6 c6 r^2 Gd(r^2), x = (alpha_d r)^2, with
                 // Gd(r^2) = alpha_d^8 e^{-x} sum_k x^k / (k+4)!  an entire function of r^2: a degree-17 polynomial in the same t as the
-                // Ewald factor (~1e-12 of Gd(0)) instead of a double-precision exp and its pre-factors (engine.hip buildEwaldPoly)
+                // Ewald factor (~1e-12 of Gd(0) at alpha_d rmax = 2.94; used where the guard of ewald_fit.h keeps it) instead of a double-precision exp and its pre-factors
                 const Real t = r2 * p.ewScale - Real(1);
                 Real gd = p.dispPoly[SNB_DISP_DEG_F64];
 #pragma unroll
@@ -194,8 +196,8 @@ __device__ __forceinline__ void tileSteps(const DirectParams<Real>& p, const typ
             }
             // Coulomb
             const Real qq = (ENERGY ? qi : qiS) * xj.w;
-            if ((MC == MC_EWALD || MC == MC_LJPME) && !ENERGY && std::is_same<Real, double>::value) {
-                // forces only: [erfc(ar)/r + 2a/sqrt(pi) e^{-(ar)^2}] = 1/r - r^2 Bt(r^2), Bt a degree-16 polynomial (~6e-12 of Bt(0)): no libm erfc / exp
+            if ((MC == MC_EWALD || MC == MC_LJPME) && !ENERGY && std::is_same<Real, double>::value && (POLYALL || (p.ewUsePoly & SNB_POLY_FORCE))) {
+                // forces only: [erfc(ar)/r + 2a/sqrt(pi) e^{-(ar)^2}] = 1/r - r^2 Bt(r^2), Bt a degree-16 polynomial (~6e-12 of Bt(0) at alpha rmax = 2.94; used where the guard of ewald_fit.h keeps it): no libm erfc / exp
                 const Real t = r2 * p.ewScale - Real(1);
                 Real bt = p.ewPoly[SNB_EW_DEG_F64];
 #pragma unroll
@@ -247,7 +249,7 @@ template <typename Real, bool ENERGY, bool FORCES = true> __device__ __forceinli
 template <typename Real, bool ENERGY, bool FORCES = true> __device__ __forceinline__ void exclusionAtomsBody(const PairListParams<Real>& p, const int blk);
 // (as in k_directPacked: the first nListBlocks work-groups of the launch run the O(N) pair lists -- exclusion corrections, then 1-4
 // exceptions -- so that their latency-bound work overlaps the tile work instead of trailing it as a 65 us launch of its own on c5)
-template <typename Real, int MC, bool WRAP, bool ENERGY>
+template <typename Real, int MC, bool WRAP, bool ENERGY, bool POLYALL>
 __global__ __launch_bounds__(256, (sizeof(Real) == 8 ? SNB_DIRECT_F64_WAVES : 4)) void k_direct(const DirectParams<Real> p, const PairListParams<Real> q, const int nExclBlocks, const int nListBlocks) {
     // (a CU-limited launch takes its list blocks LAST: its tile work-groups must be the first thing the dispatcher places on the idle CUs)
     const int listBlock = p.listsLast ? (int)blockIdx.x - ((int)gridDim.x - nListBlocks) : (int)blockIdx.x;
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 8 ? SNB_DIRECT_F64_WAVES : 4)
         Real fjx = 0, fjy = 0, fjz = 0;
 
         const bool tileE = ENERGY && p.sliceNeed[slice] != 0;      // (uniform)
-#define SNB_TILE_STEPS(E, M, SW) tileSteps<Real, MC, WRAP, E, M, SW>(p, rdPos, rdSe, pi, sei, qi, qiS, epsiS, c6i, lamC, lamL, maskWord, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj)
+#define SNB_TILE_STEPS(E, M, SW) tileSteps<Real, MC, WRAP, E, M, SW, true, POLYALL>(p, rdPos, rdSe, pi, sei, qi, qiS, epsiS, c6i, lamC, lamL, maskWord, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj)
         if (p.useSwitch && MC != MC_LJPME && MC != MC_NOCUTOFF) {
             if (tileE) { if (hasMask) SNB_TILE_STEPS(ENERGY, true, true); else SNB_TILE_STEPS(ENERGY, false, true); }
             else { if (hasMask) SNB_TILE_STEPS(false, true, true); else SNB_TILE_STEPS(false, false, true); }
@@ -455,7 +457,7 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
         v2f qqRaw = {0.f, 0.f};
         if (ENERGY) qqRaw = qiRaw * xj.w;
         if ((MC == MC_EWALD || MC == MC_LJPME) && POLY) {
-            // [erfc(ar)/r + 2a/sqrt(pi) e^{-(ar)^2}] / r^2 = 1/r^3 - Bt(r^2), Bt a degree-11 polynomial in t = r^2 * ewScale - 1: no exp, no rcp
+            // [erfc(ar)/r + 2a/sqrt(pi) e^{-(ar)^2}] / r^2 = 1/r^3 - Bt(r^2), Bt a degree-11 polynomial in t = r^2 * ewScale - 1: no exp, no rcp (POLY: where the guard of ewald_fit.h keeps it)
             const v2f t = r2 * p.ewScale - 1.0f;
             v2f bt = t * p.ewPoly[11] + p.ewPoly[10];
 #pragma unroll
@@ -842,7 +844,9 @@ template <typename Real, int MC> static TileKernel<Real> directKernel(const Dire
     if constexpr (std::is_same<Real, float>::value) {
         if (!wrap && !(energy && switches().scalarEnergyKernel) && !(p.useSwitch && MC == MC_NOCUTOFF)) {
             *packed = true;
-            const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && p.ewUsePoly;
+            // (one template switch for both polynomials: an energy step keeps them only where both passed the guard, engine.hip buildEwaldPoly)
+            const int polyNeed = energy ? (SNB_POLY_FORCE | SNB_POLY_ENERGY) : SNB_POLY_FORCE;
+            const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && (p.ewUsePoly & polyNeed) == polyNeed;
 #define SNB_PACKED(P, E, S) return p.fixed ? k_directPacked<MC, P, E, S, true> : k_directPacked<MC, P, E, S, false>
             if constexpr (MC == MC_NOCUTOFF) { if (energy) SNB_PACKED(false, true, false); else SNB_PACKED(false, false, false); }
             else if (p.useSwitch && MC != MC_LJPME) {      // (no switching function under LJPME, Q2)
@@ -856,8 +860,16 @@ template <typename Real, int MC> static TileKernel<Real> directKernel(const Dire
         }
     }
     // the scalar tile kernel: double precision, per-pair wrapping, the switches above
-    if (wrap) return energy ? k_direct<Real, MC, true, true> : k_direct<Real, MC, true, false>;
-    return energy ? k_direct<Real, MC, false, true> : k_direct<Real, MC, false, false>;
+    // double precision with every polynomial of the method in use (the benchmark point): the instantiation without tests in the loop
+    if constexpr (std::is_same<Real, double>::value && (MC == MC_EWALD || MC == MC_LJPME)) {
+        const int all = SNB_POLY_FORCE | (MC == MC_LJPME ? SNB_POLY_DISPERSION : 0);
+        if ((p.ewUsePoly & all) == all) {
+            if (wrap) return energy ? k_direct<Real, MC, true, true, true> : k_direct<Real, MC, true, false, true>;
+            return energy ? k_direct<Real, MC, false, true, true> : k_direct<Real, MC, false, false, true>;
+        }
+    }
+    if (wrap) return energy ? k_direct<Real, MC, true, true, false> : k_direct<Real, MC, true, false, false>;
+    return energy ? k_direct<Real, MC, false, true, false> : k_direct<Real, MC, false, false, false>;
 }
 template <typename Real, int MC> static bool launchDirectMC(const DirectParams<Real>& p, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
     const int myItems = p.numWork;
@@ -922,7 +934,7 @@ template <typename Real, int MC> static bool launchDirectEnergyMC(const DirectPa
     const dim3 gridAll((p.numWork + 3) / 4 + nListBlocks);
     if constexpr (std::is_same<Real, float>::value) {
         if (!wrap && !(p.useSwitch && MC == MC_NOCUTOFF)) {
-            const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && p.ewUsePoly;
+            const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && (p.ewUsePoly & SNB_POLY_ENERGY);      // (no forces: the energy polynomial alone)
 #define SNB_PACKED_E(P, S) SNB_LAUNCH_LDS((k_directPackedEnergy<MC, P, S>), gridAll, listLds, p, q, nExclBlocks, nListBlocks)
             if constexpr (MC == MC_NOCUTOFF) SNB_PACKED_E(false, false);
             else if (p.useSwitch && MC != MC_LJPME) { if (poly) SNB_PACKED_E(true, true); else SNB_PACKED_E(false, true); }

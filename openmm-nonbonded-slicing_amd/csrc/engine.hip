@@ -9,6 +9,7 @@
 #include "snb_internal.h"
 #include "switches.h"
 #include "host_lists.h"
+#include "ewald_fit.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -460,10 +461,12 @@ public:
         if (c.stream) stream = (hipStream_t)c.stream; else { HIPCHECK(hipStreamCreate(&stream)); ownStream = true; }
         ring.resize(RING);
         { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) numCUs = prop.multiProcessorCount; }
+        if (cfg.method >= SNB_Ewald) buildEwaldPoly();      // (before the kernels are chosen: polyMask decides their instantiation)
+        stats.ewald_poly_mask = polyMask;
         {      // the tile kernels a CU-limited launch can run: their allocations are asked for here, outside any capture
             DirectParams<Real> p;
             std::memset(&p, 0, sizeof(p));
-            p.useSwitch = useSwitch() ? 1 : 0; p.ewUsePoly = sw.ewaldErfc ? 0 : 1; p.fixed = fixedForces();
+            p.useSwitch = useSwitch() ? 1 : 0; p.ewUsePoly = polyMask; p.fixed = fixedForces();
             for (int w = 0; w < 2; w++) for (int e = 0; e < 2; e++) pairVgprUnits[w][e] = directVgprUnits<Real>(p, methodClass(), w != 0, e != 0);
         }
         if (sw.overlap) { dOverlap.resize(SNB_OVERLAP_INTS); HIPCHECK(hipMemsetAsync(dOverlap.p, 0, sizeof(int) * SNB_OVERLAP_INTS, stream)); }
@@ -480,7 +483,6 @@ public:
         shardBegin = cfg.shard_count > 1 ? cfg.shard_rank : 0; shardEnd = shardBegin + 1; shardPeriod = cfg.shard_count;
         // tabulated Ewald force factor: opt-in.  Measured on MI355X it only trades 4 % of the VALU instructions for LDS gathers (the packed
         // analytic erfc is already cheap) and leaves the kernel time unchanged, so the analytic form stays the default.
-        if (cfg.method >= SNB_Ewald) buildEwaldPoly();
         HIPCHECK(hipHostMalloc((void**)&hDispFlags, 64, hipHostMallocMapped));
         std::memset(hDispFlags, 0, 64);      // [0] warn, [1] overrun, [4] overruns counted on the device (k_dispFlagsReset)
         HIPCHECK(hipHostGetDevicePointer((void**)&dDispFlags, hDispFlags, 0));
@@ -533,61 +535,30 @@ public:
         if (stream2) { (void)hipEventDestroy(evFork); (void)hipEventDestroy(evJoin); (void)hipEventDestroy(evPairA); (void)hipStreamDestroy(stream2); }
         if (ownStream) (void)hipStreamDestroy(stream);
     }
-    // Real-space Ewald force factor of the single-precision forces-only pair kernel:
+    // Real-space Ewald force factor of the forces-only pair kernels:
     //   [erfc(ar)/r + 2a/sqrt(pi) exp(-(ar)^2)] / r^2 = 1/r^3 - Bt(r^2),   Bt(r^2) = [erf(ar) - 2ar/sqrt(pi) exp(-(ar)^2)] / r^3,
     // Bt is an entire function of r^2 (Bt(0) = 4a^3/(3 sqrt(pi))), so a polynomial in t = 2 r^2/r2max - 1 (Chebyshev fit over
-    // [0, (cutoff+skin)^2], converted to monomials in t, |t| <= 1) reproduces it: degree 11 to 1e-7 of Bt(0) in single precision
-    // (12 packed FMAs replace v_exp + v_rcp + the A&S erfc polynomial), degree 16 to ~6e-12 in double (replaces libm erfc + exp).  Absolute force error per pair stays below that of the A&S path at short range and
-    // below 2e-6 * qq near the cutoff (tools/ewald_poly_check.py).
-    static constexpr int EW_DEG = sizeof(Real) == 4 ? 11 : SNB_EW_DEG_F64;      // 1e-7 resp. ~6e-12 of Bt(0)
+    // [0, (cutoff+skin+0.02)^2], converted to monomials in t, |t| <= 1) reproduces it: degree 11 in single precision (12 packed FMAs replace
+    // v_exp + v_rcp + the A&S erfc polynomial), degree 16 in double (replaces libm erfc + exp).  At the benchmark's z = a (cutoff+skin+0.02)
+    // = 2.94 they are good to 1e-7 resp. ~6e-12 of Bt(0); the residual grows fast with z (degree 11: 2e-5 of Bt(0) at z = 4), so the fit
+    // (ewald_fit.h) measures it for this engine's alpha, cutoff and padding, and polyMask keeps a polynomial only where it passes the guard
+    // stated there.  The energy polynomial Et and the LJPME dispersion polynomial Gd of double precision go the same way.
+    static constexpr int EW_DEG = sizeof(Real) == 4 ? 11 : SNB_EW_DEG_F64;
+    static_assert(kEwaldFitLJPME == SNB_LJPME && kEwDegF32 == 11 && kEwDegF64 == SNB_EW_DEG_F64 && kDispDegF64 == SNB_DISP_DEG_F64, "ewald_fit.h and the kernels disagree");
+    static_assert(kPolyForce == SNB_POLY_FORCE && kPolyEnergy == SNB_POLY_ENERGY && kPolyDispersion == SNB_POLY_DISPERSION, "ewald_fit.h and the kernels disagree");
     double ewPoly[EW_DEG + 1] = {0}; double ewPolyE[14] = {0}; double dispPoly[21] = {0}; double ewR2Max = 1;
+    int polyMask = 0;      // SNB_POLY_* bits: the polynomials this engine's kernels use (DirectParams::ewUsePoly, snb_stats.ewald_poly_mask)
     void buildEwaldPoly() {
-        const double rmax = cfg.cutoff + std::max(cfg.neighbor_padding, 0.0) + 0.02, a = cfg.alpha;
-        ewR2Max = rmax * rmax;
-        auto bt = [&](double r2) {
-            const double r = std::sqrt(r2), z = a * r;
-            if (z < 2e-2) return a * a * a * (4.0 / (3.0 * std::sqrt(SNB_PI))) * (1.0 - 0.6 * z * z + (3.0 / 14.0) * z * z * z * z - (1.0 / 18.0) * z * z * z * z * z * z);
-            return (std::erf(z) - 2.0 * z / std::sqrt(SNB_PI) * std::exp(-z * z)) / (r2 * r);
-        };
-        chebyshevToMonomial(bt, EW_DEG, ewPoly);
-        // pair energies of the packed kernel: Et(r^2) = erf(a r)/r, entire in r^2 as well, Et(0) = 2a/sqrt(pi)
-        auto et = [&](double r2) {
-            const double r = std::sqrt(r2), z = a * r;
-            if (z < 1e-3) return a * (2.0 / std::sqrt(SNB_PI)) * (1.0 - z * z / 3.0 + z * z * z * z / 10.0);
-            return std::erf(z) / r;
-        };
-        chebyshevToMonomial(et, 13, ewPolyE);
-        if (cfg.method == SNB_LJPME) {      // dispersion force factor of the double-precision pair kernel
-            const double ad = cfg.alpha_d;
-            auto gd = [&](double r2) {
-                const double x = ad * ad * r2;
-                double sum = 0, term = 1.0 / 24.0;      // sum_k x^k / (k+4)!
-                for (int k = 0; k < 60; k++) { sum += term; term *= x / (k + 5); if (term < 1e-18 * sum) break; }
-                return std::pow(ad, 8.0) * std::exp(-x) * sum;
-            };
-            chebyshevToMonomial(gd, SNB_DISP_DEG_F64, dispPoly);
-        }
-    }
-    // Chebyshev interpolant of f(r^2) over [0, ewR2Max] at 96 nodes, truncated at `deg`, as monomial coefficients in t = 2 r^2/ewR2Max - 1
-    template <typename Fn> void chebyshevToMonomial(Fn f, int deg, double* out) {
-        const int M = 96;
-        std::vector<double> c(deg + 1);
-        for (int k = 0; k <= deg; k++) {
-            double acc = 0;
-            for (int j = 0; j < M; j++) { const double x = std::cos(SNB_PI * (j + 0.5) / M); acc += f(0.5 * (x + 1.0) * ewR2Max) * std::cos(SNB_PI * k * (j + 0.5) / M); }
-            c[k] = acc * 2.0 / M;
-        }
-        c[0] *= 0.5;
-        // T_0 = 1, T_1 = x, T_{k+1} = 2 x T_k - T_{k-1}
-        std::vector<double> Tm(deg + 1, 0.0), Tc(deg + 1, 0.0), Tn(deg + 1, 0.0);
-        Tm[0] = 1; if (deg >= 1) Tc[1] = 1;
-        for (int i = 0; i <= deg; i++) out[i] = 0;
-        out[0] += c[0];
-        if (deg >= 1) for (int i = 0; i <= deg; i++) out[i] += c[1] * Tc[i];
-        for (int k = 2; k <= deg; k++) {
-            for (int i = 0; i <= deg; i++) Tn[i] = (i > 0 ? 2.0 * Tc[i - 1] : 0.0) - Tm[i];
-            for (int i = 0; i <= deg; i++) { out[i] += c[k] * Tn[i]; Tm[i] = Tc[i]; Tc[i] = Tn[i]; }
-        }
+        const double rmax = cfg.cutoff + std::max(cfg.neighbor_padding, 0.0) + 0.02;
+        const EwaldFit fit = fitEwaldPolys<Real>(cfg.alpha, cfg.alpha_d, cfg.cutoff, rmax, cfg.method);
+        ewR2Max = fit.r2max;
+        for (int i = 0; i <= EW_DEG; i++) ewPoly[i] = fit.ewPoly[i];
+        for (int i = 0; i < 14; i++) ewPolyE[i] = fit.ewPolyE[i];
+        for (int i = 0; i < 21; i++) dispPoly[i] = fit.dispPoly[i];
+        // the polynomials the kernels of this precision have a branch for: single and mixed precision Bt and Et, double Bt and (LJPME) Gd
+        const int have = sizeof(Real) == 4 ? (SNB_POLY_FORCE | SNB_POLY_ENERGY) : (SNB_POLY_FORCE | (cfg.method == SNB_LJPME ? SNB_POLY_DISPERSION : 0));
+        polyMask = sw.ewaldErfc ? 0 : (sw.ewaldPolyAlways ? have : (fit.use & have));
+        if (sw.verbose) fprintf(stderr, "[snb] Ewald polynomials: force max r|dBt| %.3g (limit %.3g), energy |dEt| %.3g (%.3g), dispersion max r|dGd| %.3g (%.3g): mask %d in use\n", fit.pairF, fit.limF, fit.sysE, fit.limE, fit.pairD, fit.limD, polyMask);
     }
     bool isPme() const { return cfg.method == SNB_PME || cfg.method == SNB_LJPME; }
     bool isPeriodic() const { return cfg.method >= SNB_CutoffPeriodic; }
@@ -1674,7 +1645,7 @@ public:
         for (int i = 0; i < 14; i++) p.ewPolyE[i] = (Real)ewPolyE[i];
         for (int i = 0; i < 21; i++) p.dispPoly[i] = (Real)dispPoly[i];
         p.ewScale = (Real)(2.0 / ewR2Max);
-        p.ewUsePoly = sw.ewaldErfc ? 0 : 1;
+        p.ewUsePoly = polyMask;
         const double ic2 = 1.0 / (cfg.cutoff * cfg.cutoff), ic6 = ic2 * ic2 * ic2;
         const double dar2 = cfg.alpha_d * cfg.alpha_d * cfg.cutoff * cfg.cutoff;
         p.invCut6 = (Real)ic6; p.multShift6 = (Real)(ic6 * (1.0 - std::exp(-dar2) * (1.0 + dar2 + 0.5 * dar2 * dar2)));

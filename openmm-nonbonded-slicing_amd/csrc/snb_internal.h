@@ -41,8 +41,14 @@
 // [0, (cutoff + skin + 0.02)^2] at alpha = 2.6283/nm: degree 14 3.9e-10 of Bt(0), 15 4.7e-11, 16 5.6e-12, 17 6.6e-13; of the LJPME dispersion
 // factor Gd: 16 1.3e-11, 17 1.4e-12, 18 1.5e-13.  Round 2 ran both at degree 20 (1e-13 / 4e-15): five orders beyond the 1e-5 parity bar is
 // plenty, and each degree is one f64 FMA per pair (c5: 2.32 -> ms for the pair kernel).
+// The figures hold at that z = alpha (cutoff + skin + 0.02) = 2.94 alone and grow fast with it: ewald_fit.h measures the residuals of every
+// engine's own fit and keeps a polynomial only where they pass its guard (DirectParams::ewUsePoly).
 #define SNB_EW_DEG_F64 16
 #define SNB_DISP_DEG_F64 17
+// bits of DirectParams::ewUsePoly and of snb_stats.ewald_poly_mask (= ewald_fit.h kPoly*)
+#define SNB_POLY_FORCE 1
+#define SNB_POLY_ENERGY 2
+#define SNB_POLY_DISPERSION 4
 
 namespace snb {
 
@@ -70,9 +76,10 @@ template <typename Real> struct DirectParams {
     int nsub;
     Real cutoff2, krf, crf, alpha, alphaD, k4pe;          // k4pe = ONE_4PI_EPS0
     Real alpha2l2e;                                        // alpha^2 * log2(e)
-    Real dispPoly[21];                                     // LJPME, double, forces only: alpha_d^8 e^{-x} sum x^k/(k+4)!, x = (alpha_d r)^2, degree 20 in the same t
+    Real dispPoly[21];                                     // LJPME, double, forces only: alpha_d^8 e^{-x} sum x^k/(k+4)!, x = (alpha_d r)^2, degree 17 in the same t
     Real ewPolyE[14];                                      // energy steps of the packed kernel: erf(alpha r)/r ~ sum_k ewPolyE[k] t^k (degree 13, same t)
-    Real ewPoly[21]; Real ewScale; int ewUsePoly;         // forces-only paths: Bt(r^2) ~ sum_k ewPoly[k] t^k, t = r^2 * ewScale - 1; degree 11 (float) / 20 (double), engine.hip buildEwaldPoly
+    Real ewPoly[21]; Real ewScale;                        // forces-only paths: Bt(r^2) ~ sum_k ewPoly[k] t^k, t = r^2 * ewScale - 1; degree 11 (float) / 16 (double), ewald_fit.h
+    int ewUsePoly;                                        // SNB_POLY_* bits: the polynomials whose residuals passed the guard of ewald_fit.h; the others' terms take the erfc / exp branches
     Real invCut6, multShift6;                              // LJPME potential shifts
     int useSwitch; Real switchDist, invSwitchWidth;
     Real box[9]; Real invBoxDiag[3];                       // for the per-pair wrap variant

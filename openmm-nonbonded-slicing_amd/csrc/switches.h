@@ -46,6 +46,7 @@ struct Switches {
     int interpZSlabs = intOr("SNB_INTERP_ZSLABS", 0);      // z slabs per interpolation brick; measured on c3: 1 slab 52 us, 2 slabs 70, 4 slabs 72
     // ---- pair kernel
     bool ewaldErfc = flag("SNB_EWALD_ERFC");      // test switch: erfc / exp in the Ewald pair term instead of the polynomials
+    bool ewaldPolyAlways = flag("SNB_EWALD_POLY_ALWAYS");      // test control: the polynomials whatever their residuals, as before the guard of ewald_fit.h (SNB_EWALD_ERFC wins)
     bool scalarEnergyKernel = flag("SNB_SCALAR_ENERGY_KERNEL");      // test switch: energy steps of single precision on the scalar tile kernel
     bool noFusedLists = flag("SNB_NO_FUSED_LISTS");      // test switch: the O(N) pair lists as a launch of their own
     int directWgs = intOr("SNB_DIRECT_WGS", 0);      // cap on the tile kernel's work-groups (0: one per four work items)

@@ -29,7 +29,7 @@ def test_entry_point_is_exported_listed_and_typed(snb):
     L = capi.lib()
     assert L.snb_evaluate_atom_energies.argtypes == [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]
     assert L.snb_evaluate_atom_energies(None, 1, 1, None, 0) == capi.SNB_ERR_INVALID_ARGUMENT      # a null handle is refused before anything else
-    assert capi.SNB_ABI_VERSION == 7 and L.snb_abi_version() == 7      # additive
+    assert capi.SNB_ABI_VERSION == 8 and L.snb_abi_version() == 8      # additive
 
 
 @pytest.fixture(scope="module", params=["PME", "CutoffPeriodic"])

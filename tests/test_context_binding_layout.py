@@ -24,7 +24,7 @@ def test_context_binding_layout_matches_c_compiler(snb, tmp_path):
 
 def test_binding_entry_points_are_declared(snb):
     capi = snb.capi
-    assert capi.SNB_ABI_VERSION == 7
+    assert capi.SNB_ABI_VERSION == 8
     assert {"snb_bind_context", "snb_context_order_changed"} <= set(capi.SYMBOLS)
     L = capi.lib()
     assert L.snb_bind_context(None, None) == capi.SNB_ERR_INVALID_ARGUMENT      # a null handle is refused before anything else

@@ -43,8 +43,8 @@ def test_frame_entry_points_are_exported_and_listed(snb):
     assert L.snb_get_frame_stats(None, None) == capi.SNB_ERR_INVALID_ARGUMENT
 
 
-def test_abi_version_is_still_7(snb):
-    assert snb.capi.SNB_ABI_VERSION == 7
-    assert snb.capi.lib().snb_abi_version() == 7
+def test_abi_version_is_8(snb):
+    assert snb.capi.SNB_ABI_VERSION == 8
+    assert snb.capi.lib().snb_abi_version() == 8
     with open(os.path.join(ROOT, "include", "snb.h"), encoding="utf-8") as f:
-        assert "#define SNB_ABI_VERSION 7\n" in f.read()
+        assert "#define SNB_ABI_VERSION 8\n" in f.read()

@@ -25,7 +25,7 @@ def test_struct_layout_matches_header(snb):
     capi = snb.capi
     # sizes follow from the field lists in include/snb.h (natural alignment)
     assert ctypes.sizeof(capi.SnbConfig) == 8 * 4 + 4 * 8 + 6 * 4 + 8 + 3 * 4 + 4 + 8 + 3 * 4 + 2 * 4 + 4 + 8
-    assert ctypes.sizeof(capi.SnbStats) == 7 * 8 + 6 * 4 + 4 * 8 + 3 * 8 + 8 + 8 + 8 + 16 * 8 + 16 * 8 + 8
+    assert ctypes.sizeof(capi.SnbStats) == 7 * 8 + 6 * 4 + 4 * 8 + 3 * 8 + 8 + 8 + 8 + 16 * 8 + 16 * 8 + 8 + 8
 
 
 def test_struct_layout_matches_c_compiler(snb, tmp_path):
@@ -196,5 +196,10 @@ def test_hot_kernels_use_no_scratch(snb):
                "k_fftZ<double", "k_interpolateBricks<double", "k_interpolate<", "k_pairLists<", "k_ewald", "k_spread<")
     unexpected = {n: v for n, v in notes.items() if v[0] > 0 and not any(a in n for a in allowed)}
     assert not unexpected, unexpected
+    # the double-precision tile kernel, with and without the run-time tests of the Ewald polynomials (template argument POLYALL):
+    # neither form may spill (the testing instantiations reach 244 of 256 registers)
+    tile64 = {n: v for n, v in notes.items() if n.startswith("void k_direct<double")}
+    assert len(tile64) == 24, sorted(tile64)
+    assert not {n: v for n, v in tile64.items() if v[0] > 0 or v[2] > 0}, tile64
     users = sorted((v[0], n) for n, v in notes.items() if v[0] > 0)
     print("kernels with scratch: %d of %d; largest: %s" % (len(users), len(notes), users[-3:]))
