@@ -347,6 +347,44 @@ snb_status snb_evaluate_atom_energies(snb_handle h, int32_t include_direct, int3
 snb_status snb_evaluate_atom_forces(snb_handle h, int32_t include_direct, int32_t include_reciprocal,
                                     double* atom_forces /* [n_atoms][n_subsets][2][3], USER order */, int32_t out_is_device);
 
+/* -- per-group interaction energies over stored frames ----------------------------------------- */
+/* The product of the two calls above: the atom-energy table summed over lists of atoms (residues, a ligand, first-shell waters), for every
+ * frame of a stored trajectory, reduced on the device --
+ *     group_energies[f][g][J][t] = sum_{i in atoms(g)} A_f[i][J][t]
+ * with A_f the table of snb_evaluate_atom_energies at frame f: the same attribution, raw (lambda-independent) values, effective parameters,
+ * and the long-range dispersion correction left out.  Groups are lists (CSR: group_start[G + 1], group_atoms, USER indices): they may
+ * overlap, leave atoms out, be empty (a row of zeros), and an index listed twice counts twice.  Every entry of the output is written.  The
+ * sums use no atomics: a row is a function of the frame's table alone (the table itself is accumulated with double atomics).
+ * With frames given the call follows the contract of snb_evaluate_frames: everything is checked before anything is enqueued; the list of
+ * frame f + 1 is built beside the pass of frame f, or in line, by the same rules; host frames go through the pinned staging; host output
+ * costs one synchronisation, at the end; device output is complete in stream order; afterwards positions, box, lambdas and mask are the
+ * caller's and the next snb_execute rebuilds; no step graph is captured or updated; frame steps count in snb_stats.n_rebuilds and in no
+ * timer; snb_get_frame_stats counts the batch and its frames.  With positions == NULL (n_frames must be 1) it is ONE evaluation of the
+ * engine's current box and positions and behaves as snb_evaluate_atom_energies behaves, a bound context included.
+ * In both forms it writes ONLY its output: the forces (snb_get_forces), the buffer of snb_set_force_output, a binding's buffers and the
+ * engine's slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) stay bit for bit what they were.
+ * NULL batch, handle, group_energies, group_start or group_atoms, n_groups < 1, a group_start that does not begin at 0 or decreases, an
+ * atom index outside [0, n_atoms) (snb_last_error names the group), both include flags 0, a negative n_frames, positions == NULL with
+ * n_frames != 1: SNB_ERR_INVALID_ARGUMENT.  shard_count > 1, SNB_Ewald with include_reciprocal: SNB_ERR_UNSUPPORTED.  n_frames == 0 (after
+ * these checks): SNB_OK, no work.  Frames given while a context is bound: SNB_ERR_STATE.  Box errors: as snb_evaluate_frames, with the
+ * frame index.  The working memory (the table over the sorted atoms, the chunk sums) is allocated at the first call. */
+typedef struct {
+    int32_t        n_frames;
+    const void*    positions;        /* [F][N][3], or [F][N][4] when stride4 != 0; USER atom order; float or double by is_double;
+                                        NULL: one evaluation of the engine's CURRENT box and positions (n_frames must be 1) */
+    int32_t        is_device;        /* != 0: device pointer on the engine's device, valid until the engine's stream has passed the batch */
+    int32_t        is_double;
+    int32_t        stride4;
+    const double*  boxes;            /* HOST [F][9], reduced form, or NULL: the engine's current box for every frame */
+    int32_t        include_direct, include_reciprocal;
+    int32_t        n_groups;         /* G >= 1 */
+    const int32_t* group_start;      /* HOST [G + 1], group_start[0] == 0, non-decreasing */
+    const int32_t* group_atoms;      /* HOST [group_start[G]], USER atom indices */
+    double*        group_energies;   /* [F][G][n_subsets][2] raw (Coulomb, vdW) */
+    int32_t        out_is_device;
+} snb_group_batch;
+snb_status snb_evaluate_group_energies(snb_handle h, const snb_group_batch* b);
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

@@ -447,6 +447,91 @@ class HipCalcSlicedNonbondedForceKernel:
             out[:, mask == 0] = np.nan
         return out if states is None else (out, states)
 
+    @staticmethod
+    def groupsToCSR(groups):
+        """Lists of atom indices, one per group, as the CSR pair of snb_group_batch: (group_start int32 [G + 1], group_atoms int32
+        [group_start[G]]).  The lists are kept as given: overlapping, empty, with repeated indices."""
+        lists = [np.asarray(list(g), dtype=np.int64).reshape(-1) for g in groups]
+        start = np.zeros(len(lists) + 1, dtype=np.int32)
+        if lists:
+            start[1:] = np.cumsum([len(a) for a in lists])
+        atoms = np.concatenate(lists).astype(np.int32) if start[-1] > 0 else np.zeros(0, dtype=np.int32)
+        return start, np.ascontiguousarray(atoms)
+
+    def _groupBatch(self, groups, includeDirect, includeReciprocal):
+        start, atoms = self.groupsToCSR(groups)
+        if len(start) < 2:
+            raise OpenMMException("group energies: at least one group")
+        b = _capi.SnbGroupBatch()
+        if len(atoms) == 0:
+            atoms = np.zeros(1, dtype=np.int32)      # (only empty groups: group_atoms must still be an address)
+        b.n_groups = len(start) - 1; b.group_start = _ip(start); b.group_atoms = _ip(atoms)
+        b.include_direct = int(bool(includeDirect)); b.include_reciprocal = int(bool(includeReciprocal))
+        return b, (start, atoms)      # (the arrays the batch points into: the caller keeps them until the call has returned)
+
+    def computeGroupEnergies(self, context, groups, includeDirect=True, includeReciprocal=True, devicePointer=None):
+        """Per-group interaction energies with every subset at the context's positions, box and parameters (include/snb.h,
+        snb_evaluate_group_energies with positions == NULL): the table of computeAtomEnergies summed over each list of atom indices in
+        ``groups`` on the device, (G, n_subsets, 2) -- what groupAtomEnergies(computeAtomEnergies(...), groups) gives, without the per-atom
+        table crossing to the host.  devicePointer: address of a double [G][n_subsets][2] array on the engine's device that takes the
+        result (complete in stream order); then None is returned."""
+        self._push_state(context)
+        b, keep = self._groupBatch(groups, includeDirect, includeReciprocal)
+        b.n_frames = 1
+        out = None
+        if devicePointer is not None:
+            b.group_energies = ctypes.c_void_p(int(devicePointer)); b.out_is_device = 1
+        else:
+            out = np.zeros((b.n_groups, self.numSubsets, 2))
+            b.group_energies = out.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        self._check(self._lib.snb_evaluate_group_energies(self._h, ctypes.byref(b)))
+        return out
+
+    def computeGroupEnergiesForFrames(self, context, groups, positions=None, boxes=None, includeDirect=True, includeReciprocal=True, positionsDevicePointer=None,
+                                      numFrames=None, devicePointer=None):
+        """Per-group interaction energies [F][G][n_subsets][2] of F stored frames in one call (include/snb.h, snb_evaluate_group_energies):
+        the Coulomb and vdW energy of every residue with the ligand subset frame by frame, a per-residue decomposition over a trajectory --
+        the frame pipeline of computeSliceEnergiesForFrames with the atom-energy pass as its step and the sum over each group's atoms on the
+        device.  groups: a list of lists of atom indices, as in groupAtomEnergies.  positions, boxes, positionsDevicePointer, numFrames: as
+        in computeSliceEnergiesForFrames.  devicePointer: address of a double [F][G][n_subsets][2] array on the engine's device that takes
+        the result (complete in stream order); then None is returned.  Parameters are pushed from the context first; the context's own
+        positions, the forces and the slice energies of the last steps stay as they are."""
+        self._push_parameters(context.getParameters())
+        box = np.ascontiguousarray(context.getPeriodicBoxVectors(), dtype=np.float64).reshape(9)
+        self._check(self._lib.snb_set_box(self._h, _dp(box)))
+        b, keep = self._groupBatch(groups, includeDirect, includeReciprocal)
+        if positionsDevicePointer is not None:
+            if positions is not None or numFrames is None:
+                raise OpenMMException("computeGroupEnergiesForFrames: positionsDevicePointer goes with numFrames and without positions")
+            ptr, isDouble = positionsDevicePointer
+            F = int(numFrames)
+            b.positions = ctypes.c_void_p(int(ptr)); b.is_device = 1; b.is_double = int(bool(isDouble))
+        else:
+            if positions is None:
+                raise OpenMMException("computeGroupEnergiesForFrames: positions or positionsDevicePointer must be given (computeGroupEnergies evaluates the context's own state)")
+            pos = np.asarray(positions)
+            if pos.dtype != np.float32:
+                pos = pos.astype(np.float64, copy=False)
+            pos = np.ascontiguousarray(pos)
+            if pos.ndim != 3 or pos.shape[1:] != (self.numParticles, 3):
+                raise OpenMMException("computeGroupEnergiesForFrames: positions must be [F][%d][3]" % self.numParticles)
+            F = pos.shape[0]
+            b.positions = pos.ctypes.data_as(ctypes.c_void_p); b.is_device = 0; b.is_double = int(pos.dtype == np.float64)
+        b.n_frames = F; b.stride4 = 0
+        if boxes is not None:
+            bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 9))
+            if bx.shape[0] != F:
+                raise OpenMMException("computeGroupEnergiesForFrames: one box per frame")
+            b.boxes = _dp(bx)
+        out = None
+        if devicePointer is not None:
+            b.group_energies = ctypes.c_void_p(int(devicePointer)); b.out_is_device = 1
+        else:
+            out = np.zeros((F, b.n_groups, self.numSubsets, 2))
+            b.group_energies = out.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        self._check(self._lib.snb_evaluate_group_energies(self._h, ctypes.byref(b)))
+        return out
+
     def getFrameStats(self):
         st = _capi.SnbFrameStats()
         self._check(self._lib.snb_get_frame_stats(self._h, ctypes.byref(st)))
@@ -554,6 +639,9 @@ class SlicedNonbondedForceImpl:
     def getAtomForces(self, context, **options):
         return self.kernel.computeAtomForces(context, **options)
 
+    def getGroupEnergies(self, context, groups, **options):
+        return self.kernel.computeGroupEnergies(context, groups, **options)
+
 
 class System:
     def __init__(self):
@@ -649,6 +737,15 @@ class Context:
         for impl in self._impls:
             if impl.owner is force:
                 return impl.getAtomEnergies(self, **options)
+        raise OpenMMException("force not in this context")
+
+    def getGroupEnergies(self, force, groups, **options):
+        """Per-group interaction energies of ``force`` with every subset, (G, n_subsets, 2): HipCalcSlicedNonbondedForceKernel.computeGroupEnergies."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        for impl in self._impls:
+            if impl.owner is force:
+                return impl.getGroupEnergies(self, groups, **options)
         raise OpenMMException("force not in this context")
 
     def getAtomForces(self, force, **options):

@@ -115,6 +115,7 @@ struct EngineBase {
     virtual void evaluateFrames(const snb_frame_batch*) = 0;
     virtual void evaluateAtomEnergies(int, int, double*, int) = 0;
     virtual void evaluateAtomForces(int, int, double*, int) = 0;
+    virtual void evaluateGroupEnergies(const snb_group_batch*) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
@@ -1460,39 +1461,39 @@ public:
             frameDev[k].resize(frameBytes);
         }
     }
-    void evaluateFrames(const snb_frame_batch* b) override {
-        const auto t0 = std::chrono::steady_clock::now();
-        // ---- everything is checked before anything is enqueued or changed
-        if (b->n_frames < 0) { err = "snb_evaluate_frames: negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (ctx.on) { err = "snb_evaluate_frames: a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
-        if (cfg.shard_count > 1) { err = "snb_evaluate_frames: not available with shard_count > 1"; throw (int)SNB_ERR_UNSUPPORTED; }
-        const int F = b->n_frames;
-        if (F == 0) return;
-        if (!b->positions || !b->slice_energies) { err = "snb_evaluate_frames: positions and slice_energies must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (b->mode != 1 && b->mode != 2) { err = "snb_evaluate_frames: mode must be 1 (every slice) or 2 (the slices of snb_set_energy_slices)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        const int K = b->n_states;
-        if (K < 0 || (K > 0 && (b->mode != 1 || !b->state_lambdas || !b->state_energies))) { err = "snb_evaluate_frames: lambda states need mode 1, state_lambdas and state_energies"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (!haveParticles) throw HipError{"snb_evaluate_frames: particles were not set"};
-        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
-        const bool frameBoxes = isPeriodic() && b->boxes != nullptr;
+    // The frames of a batch: what snb_frame_batch and snb_group_batch say about them (who: the entry point, for the messages)
+    struct FrameInput { const char* who; int F; const void* positions; bool hostFrames, isDouble, stride4; const double* boxes; };
+    // ---- everything about the frames is checked before anything is enqueued or changed
+    void checkFrames(const FrameInput& in, bool recip) {
+        const std::string who = in.who; const int F = in.F;
+        if (!haveParticles) throw HipError{who + ": particles were not set"};
+        const bool frameBoxes = isPeriodic() && in.boxes != nullptr;
         if (isPeriodic()) {
-            if (!frameBoxes && !haveBox) throw HipError{"snb_evaluate_frames: box was not set"};
+            if (!frameBoxes && !haveBox) throw HipError{who + ": box was not set"};
             const double minAllowed = 1.999999 * cfg.cutoff;
             for (int f = 0; f < (frameBoxes ? F : 1); f++) {
-                const double* x = frameBoxes ? b->boxes + 9 * (size_t)f : box;
-                if (x[1] != 0 || x[2] != 0 || x[5] != 0) throw HipError{"snb_evaluate_frames: frame " + std::to_string(f) + ": box vectors must be in reduced (lower triangular) form"};
-                if (!(x[0] >= minAllowed && x[4] >= minAllowed && x[8] >= minAllowed)) { err = "snb_evaluate_frames: frame " + std::to_string(f) + ": The periodic box size has decreased to less than twice the nonbonded cutoff."; throw (int)SNB_ERR_BOX_TOO_SMALL; }
-                if (cfg.method == SNB_Ewald && recip && (x[3] != 0 || x[6] != 0 || x[7] != 0)) { err = "snb_evaluate_frames: frame " + std::to_string(f) + ": SlicedNonbondedForce: Ewald is not supported with non-rectangular boxes.  Use PME instead."; throw (int)SNB_ERR_UNSUPPORTED; }
+                const double* x = frameBoxes ? in.boxes + 9 * (size_t)f : box;
+                if (x[1] != 0 || x[2] != 0 || x[5] != 0) throw HipError{who + ": frame " + std::to_string(f) + ": box vectors must be in reduced (lower triangular) form"};
+                if (!(x[0] >= minAllowed && x[4] >= minAllowed && x[8] >= minAllowed)) { err = who + ": frame " + std::to_string(f) + ": The periodic box size has decreased to less than twice the nonbonded cutoff."; throw (int)SNB_ERR_BOX_TOO_SMALL; }
+                if (cfg.method == SNB_Ewald && recip && (x[3] != 0 || x[6] != 0 || x[7] != 0)) { err = who + ": frame " + std::to_string(f) + ": SlicedNonbondedForce: Ewald is not supported with non-rectangular boxes.  Use PME instead."; throw (int)SNB_ERR_UNSUPPORTED; }
             }
         }
         if (cfg.method == SNB_Ewald && recip && (cfg.kmax[0] < 1 || cfg.kmax[1] < 1 || cfg.kmax[2] < 1)) { err = "Ewald: kmax must be given explicitly (snb_config.kmax)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+    }
+    // The frame loop of a batch, for any kind of step: step(f) enqueues, on `stream`, what is evaluated at frame f -- the lists in use are
+    // that frame's, box and devUserPos are set -- and everything it enqueues precedes evFrameStep[f & 1]: the build of frame f + 2 overwrites
+    // the list set it reads.  finish() enqueues what follows the last frame and returns whether it synchronised (host output).  The engine's
+    // own state is put back when the batch is through, or has failed.
+    template <typename Step, typename Finish>
+    void runFrames(const FrameInput& in, const std::chrono::steady_clock::time_point t0, Step&& step, Finish&& finish) {
+        const int F = in.F;
+        const bool frameBoxes = isPeriodic() && in.boxes != nullptr;
         // ---- the engine's own state, put back when the batch is through
         const void* const savedPos = devUserPos; const int savedIsDouble = posIsDouble, savedStride4 = posStride4; const bool savedHavePos = havePositions, savedHaveBox = haveBox;
         double savedBox[9]; for (int i = 0; i < 9; i++) savedBox[i] = box[i];
         const long long discardedBefore = sideDiscarded; const int savedPredict = npadPredict;
-        const size_t rowLen = (size_t)S * 2;
-        const bool hostFrames = b->is_device == 0, hostOut = b->out_is_device == 0;
-        const size_t frameBytes = (size_t)N * (b->stride4 ? 4 : 3) * (b->is_double ? 8 : 4);
+        const bool hostFrames = in.hostFrames;
+        const size_t frameBytes = (size_t)N * (in.stride4 ? 4 : 3) * (in.isDouble ? 8 : 4);
         auto restore = [&]() {
             devUserPos = savedPos; posIsDouble = savedIsDouble; posStride4 = savedStride4; havePositions = savedHavePos; haveBox = savedHaveBox;
             for (int i = 0; i < 9; i++) box[i] = savedBox[i];
@@ -1505,9 +1506,7 @@ public:
             if (sidePending) cancelSideBuild();      // (an MD side build in flight: its list would come into use after frames it knows nothing of)
             keepLastForces();      // before the first frame's rebuild re-sorts the atoms
             ensureFrameResources(hostFrames, frameBytes);
-            double* rows = b->slice_energies;
-            if (hostOut) { frameRows.resize((size_t)F * rowLen); rows = frameRows.p; }
-            posIsDouble = b->is_double ? 1 : 0; posStride4 = b->stride4 ? 1 : 0; havePositions = true; plainSort = true;
+            posIsDouble = in.isDouble ? 1 : 0; posStride4 = in.stride4 ? 1 : 0; havePositions = true; plainSort = true;
             // The batch's own padded-count prediction: unrelated frames move the count further than consecutive MD rebuilds do (MD: last count
             // + 0.4 % + 8 blocks), so a batch sizes the arrays by the last exact count + 3 % + 32 blocks, from its first frame's build on, and
             // keeps that size while a frame's count leaves it 8 spare blocks -- a prediction that moved with every new maximum would no longer
@@ -1522,13 +1521,13 @@ public:
             predictForFrames();
             long long nBeside = 0, nInLine = 0;
             HIPCHECK(hipEventRecord(evBatchStart, stream));      // (staging slots and the shadow set may still be read by what was enqueued before the batch)
-            auto frameBox = [&](int f) { return frameBoxes ? b->boxes + 9 * (size_t)f : savedBox; };
+            auto frameBox = [&](int f) { return frameBoxes ? in.boxes + 9 * (size_t)f : savedBox; };
             auto sameBox = [&](int f, int g) { return std::memcmp(frameBox(f), frameBox(g), 9 * sizeof(double)) == 0; };
             // the event behind the last step that read what frame g is about to overwrite (its staging slot, the shadow set): the step of frame g - 2
             auto freeEvent = [&](int g) { return g >= 2 ? evFrameStep[g & 1] : evBatchStart; };
             // frame g on the device: the caller's own buffer, or its staging slot, filled by the copy stream
             auto stage = [&](int g) -> const void* {
-                const unsigned char* src = static_cast<const unsigned char*>(b->positions) + (size_t)g * frameBytes;
+                const unsigned char* src = static_cast<const unsigned char*>(in.positions) + (size_t)g * frameBytes;
                 if (!hostFrames) return src;
                 const int slot = g & 1;
                 if (frameUpPending[slot]) { HIPCHECK(hipEventSynchronize(evFrameUp[slot])); frameUpPending[slot] = false; }      // (the copy of frame g - 2 out of this pinned slot: long done)
@@ -1554,10 +1553,7 @@ public:
                 }
                 if (gpuBuilt) predictForFrames();
                 stepsSinceRebuild++;
-                energySelective = b->mode == 2; ctxAddTotal = false;
-                frameRow = rows + (size_t)f * rowLen;
-                enqueueStep(true, direct, recip, nullptr, StepForces::None);      // plain launches, never stamped: no step graph is captured or updated
-                frameRow = nullptr;
+                step(f);      // plain launches, never stamped: no step graph is captured or updated
                 HIPCHECK(hipEventRecord(evFrameStep[f & 1], stream));
                 if (f + 1 < F) {
                     cur = stage(f + 1);
@@ -1569,26 +1565,55 @@ public:
                     if (hostFrames) HIPCHECK(hipStreamWaitEvent(stream, evFrameUp[(f + 1) & 1], 0));
                 }
             }
-            double* states = b->state_energies;
-            if (K > 0) {
-                pinned.upload(dStateLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * rowLen), stream);
-                if (hostOut) { frameStates.resize((size_t)F * K); states = frameStates.p; }
-                launchFrameStateEnergies(rows, dStateLambdas.p, states, F, K, (int)rowLen, stream);
-            }
-            energyPending = true;      // (the engine's own buffer holds the last frame's sums)
             fstats.n_batches++; fstats.n_frames += F; fstats.n_built_beside += nBeside; fstats.n_built_in_line += nInLine; fstats.n_side_discarded += sideDiscarded - discardedBefore; fstats.last_batch_ms = 0;
-            if (hostOut) {      // the one synchronisation of a batch with host output
-                HIPCHECK(hipMemcpyAsync(b->slice_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
-                if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_energies, states, sizeof(double) * (size_t)F * K, hipMemcpyDeviceToHost, stream));
-                HIPCHECK(hipStreamSynchronize(stream));
-                fstats.last_batch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            }
+            if (finish()) fstats.last_batch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         } catch (...) {
             if (sidePending) { try { cancelSideBuild(); } catch (...) {} }
             restore();
             throw;
         }
         restore();
+    }
+    void evaluateFrames(const snb_frame_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (b->n_frames < 0) { err = "snb_evaluate_frames: negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (ctx.on) { err = "snb_evaluate_frames: a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        if (cfg.shard_count > 1) { err = "snb_evaluate_frames: not available with shard_count > 1"; throw (int)SNB_ERR_UNSUPPORTED; }
+        const int F = b->n_frames;
+        if (F == 0) return;
+        if (!b->positions || !b->slice_energies) { err = "snb_evaluate_frames: positions and slice_energies must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (b->mode != 1 && b->mode != 2) { err = "snb_evaluate_frames: mode must be 1 (every slice) or 2 (the slices of snb_set_energy_slices)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const int K = b->n_states;
+        if (K < 0 || (K > 0 && (b->mode != 1 || !b->state_lambdas || !b->state_energies))) { err = "snb_evaluate_frames: lambda states need mode 1, state_lambdas and state_energies"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
+        const FrameInput in{"snb_evaluate_frames", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
+        checkFrames(in, recip);
+        const size_t rowLen = (size_t)S * 2;
+        const bool hostOut = b->out_is_device == 0;
+        double* rows = b->slice_energies;
+        if (hostOut) { frameRows.resize((size_t)F * rowLen); rows = frameRows.p; }
+        runFrames(in, t0,
+            [&](int f) {      // one energy-only step, its finish kernel writing the frame's row as well
+                energySelective = b->mode == 2; ctxAddTotal = false;
+                frameRow = rows + (size_t)f * rowLen;
+                enqueueStep(true, direct, recip, nullptr, StepForces::None);
+                frameRow = nullptr;
+            },
+            [&]() {
+                double* states = b->state_energies;
+                if (K > 0) {
+                    pinned.upload(dStateLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * rowLen), stream);
+                    if (hostOut) { frameStates.resize((size_t)F * K); states = frameStates.p; }
+                    launchFrameStateEnergies(rows, dStateLambdas.p, states, F, K, (int)rowLen, stream);
+                }
+                energyPending = true;      // (the engine's own buffer holds the last frame's sums)
+                if (!hostOut) return false;
+                // the one synchronisation of a batch with host output
+                HIPCHECK(hipMemcpyAsync(b->slice_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+                if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_energies, states, sizeof(double) * (size_t)F * K, hipMemcpyDeviceToHost, stream));
+                HIPCHECK(hipStreamSynchronize(stream));
+                return true;
+            });
     }
     void getFrameStats(snb_frame_stats* o) override { *o = fstats; }
 
@@ -1839,17 +1864,10 @@ public:
     // mesh held (what a rank that owns all meshes runs), then the value part of the interpolation per (atom, mesh).
     // ------------------------------------------------------------------------------------------
     DevBuf<double> atomTab, atomOut;      // sorted-order working table [Npad][nsub][2]; user-order staging of a host result (both allocated at the first call)
-    void evaluateAtomEnergies(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
-        if (!out) { err = "snb_evaluate_atom_energies: atom_energies is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (!includeDirect && !includeRecip) { err = "snb_evaluate_atom_energies: neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (cfg.shard_count > 1) { err = "snb_evaluate_atom_energies: not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
-        if (cfg.method == SNB_Ewald && includeRecip) { err = "snb_evaluate_atom_energies: the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
-        beginExecute(false, includeRecip);
-        const size_t tabN = (size_t)Npad * nsub * 2, outN = (size_t)N * nsub * 2;
-        atomTab.resize(tabN);
-        if (!outIsDevice) atomOut.resize(outN);
-        double* const dst = outIsDevice ? out : atomOut.p;
-        launchZeroFill(atomTab.p, sizeof(double) * tabN, stream);
+    // The pass that fills atomTab (sized by the caller, at least [Npad][nsub][2]) for the lists, box and positions in use: what
+    // snb_evaluate_atom_energies runs between the neighbour-list rules and its finish kernel, and the step of a group batch's frame.
+    void enqueueAtomPass(bool includeDirect, bool includeRecip) {
+        launchZeroFill(atomTab.p, sizeof(double) * (size_t)Npad * nsub * 2, stream);
         // the position-gather pass of a step that clears nothing: sorted positions, the Coulomb-mesh cells, the displacement watch
         const bool recip = includeRecip && isPme() && nGrids > 0;
         GatherCells<Real> gc;
@@ -1891,14 +1909,99 @@ public:
                 launchAtomPotential<Real>(pp, atomTab.p, stream);
             }
         }
-        SliceFinish f = makeSliceFinish(includeDirect != 0, includeRecip != 0);
-        f.dispCoef = nullptr;      // the long-range dispersion correction is a per-slice constant: not attributed
-        launchAtomFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, N, nsub, f, dst, stream);
+    }
+    // closed-form terms of a completed table row (the long-range dispersion correction is a per-slice constant: not attributed)
+    SliceFinish makeAtomFinish(bool includeDirect, bool includeRecip) const { SliceFinish f = makeSliceFinish(includeDirect, includeRecip); f.dispCoef = nullptr; return f; }
+    void evaluateAtomEnergies(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
+        if (!out) { err = "snb_evaluate_atom_energies: atom_energies is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (!includeDirect && !includeRecip) { err = "snb_evaluate_atom_energies: neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (cfg.shard_count > 1) { err = "snb_evaluate_atom_energies: not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        if (cfg.method == SNB_Ewald && includeRecip) { err = "snb_evaluate_atom_energies: the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        beginExecute(false, includeRecip);
+        const size_t tabN = (size_t)Npad * nsub * 2, outN = (size_t)N * nsub * 2;
+        atomTab.resize(tabN);
+        if (!outIsDevice) atomOut.resize(outN);
+        double* const dst = outIsDevice ? out : atomOut.p;
+        enqueueAtomPass(includeDirect != 0, includeRecip != 0);
+        launchAtomFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, N, nsub, makeAtomFinish(includeDirect != 0, includeRecip != 0), dst, stream);
         endExecute();
         if (!outIsDevice) {
             HIPCHECK(hipMemcpyAsync(out, atomOut.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
             HIPCHECK(hipStreamSynchronize(stream));
         }
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Per-group interaction energies over stored frames (snb_evaluate_group_energies): the table above summed over
+    // lists of atoms, on the device, per frame.  With frames: the frame loop of snb_evaluate_frames (runFrames) with the atom pass and the
+    // group finish as the step.  Without: one evaluation under the rules of evaluateAtomEnergies.  Writes only its output: the working table,
+    // the chunk sums and the staging of a host result are its own (atomTab is shared with evaluateAtomEnergies, which refills it).
+    // ------------------------------------------------------------------------------------------
+    DevBuf<int> dGroupPlan; DevBuf<double> groupPartial, groupOut;
+    void evaluateGroupEnergies(const snb_group_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::string who = "snb_evaluate_group_energies";
+        // ---- everything is checked before anything is enqueued or changed
+        if (!b->group_energies || !b->group_start || !b->group_atoms) { err = who + ": group_energies, group_start and group_atoms must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const int G = b->n_groups;
+        if (G < 1) { err = who + ": n_groups must be at least 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (b->group_start[0] != 0) { err = who + ": group_start[0] must be 0"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        for (int g = 0; g < G; g++) if (b->group_start[g + 1] < b->group_start[g]) { err = who + ": group_start decreases at group " + std::to_string(g); throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        for (int g = 0; g < G; g++) for (int e = b->group_start[g]; e < b->group_start[g + 1]; e++) {
+            const int a = b->group_atoms[e];
+            if (a < 0 || a >= N) { err = who + ": group " + std::to_string(g) + ": atom index " + std::to_string(a) + " is outside [0, " + std::to_string(N) + ")"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        }
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
+        if (!direct && !recip) { err = who + ": neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (b->n_frames < 0) { err = who + ": negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (cfg.shard_count > 1) { err = who + ": not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        if (cfg.method == SNB_Ewald && recip) { err = who + ": the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        const int F = b->n_frames;
+        if (F == 0) return;
+        if (!b->positions && F != 1) { err = who + ": positions == NULL evaluates the engine's current state: n_frames must be 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (b->positions && ctx.on) { err = who + ": frames were given while a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        const FrameInput in{"snb_evaluate_group_energies", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
+        if (b->positions) checkFrames(in, recip);
+        // ---- the lists, packed with the work lists of the two mappings: one upload per call, through the pinned ring
+        GroupPlan plan;
+        planGroups(G, b->group_start, plan);
+        std::copy(b->group_atoms, b->group_atoms + b->group_start[G], plan.packed.begin() + plan.offAtoms);
+        const size_t rowLen = (size_t)G * nsub * 2;
+        const bool hostOut = b->out_is_device == 0;
+        double* rows = b->group_energies;
+        auto prepare = [&]() {
+            pinned.upload(dGroupPlan, plan.packed, stream);
+            groupPartial.resize((size_t)std::max(plan.nChunks, 1) * nsub * 2);
+            if (hostOut) { groupOut.resize((size_t)F * rowLen); rows = groupOut.p; }
+        };
+        auto groupFinish = [&](int f) {
+            launchGroupFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, nsub, makeAtomFinish(direct, recip), plan, dGroupPlan.p, groupPartial.p, rows + (size_t)f * rowLen, stream);
+        };
+        auto deliver = [&]() {
+            if (!hostOut) return false;
+            HIPCHECK(hipMemcpyAsync(b->group_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+            return true;
+        };
+        if (!b->positions) {      // the engine's current state, as snb_evaluate_atom_energies takes it
+            beginExecute(false, recip);
+            prepare();
+            atomTab.resize((size_t)Npad * nsub * 2);
+            enqueueAtomPass(direct, recip);
+            groupFinish(0);
+            endExecute();
+            deliver();
+            return;
+        }
+        prepare();
+        runFrames(in, t0,
+            [&](int f) {
+                // (sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
+                atomTab.resize((size_t)std::max(Npad, npadPredict) * nsub * 2);
+                enqueueAtomPass(direct, recip);
+                groupFinish(f);      // before evFrameStep[f & 1]: it reads userToSorted, blockSubset, posq and sigeps of this frame's list set
+            },
+            deliver);
     }
 
     // ------------------------------------------------------------------------------------------
@@ -2210,6 +2313,10 @@ snb_status snb_evaluate_atom_energies(snb_handle h, int32_t includeDirect, int32
 }
 snb_status snb_evaluate_atom_forces(snb_handle h, int32_t includeDirect, int32_t includeRecip, double* atomForces, int32_t outIsDevice) {
     return guard(h, [&] { h->impl->evaluateAtomForces(includeDirect, includeRecip, atomForces, outIsDevice); });
+}
+snb_status snb_evaluate_group_energies(snb_handle h, const snb_group_batch* b) {
+    if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_energies: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
+    return guard(h, [&] { h->impl->evaluateGroupEnergies(b); });
 }
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 

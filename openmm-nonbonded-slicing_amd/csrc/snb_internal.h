@@ -329,6 +329,16 @@ template <typename Real> void launchAtomPairs(const DirectParams<Real>& p, int m
 template <typename Real> void launchAtomPotential(const PmeParams<Real>& p, double* tab, hipStream_t s);   // + q_i psi_J(r_i) from the unmixed real-space potentials of p
 template <typename Real> void launchAtomFinish(const double* tab, const int* userToSorted, const int* blockSubset, const typename Vec<Real>::T4* posq, const typename Vec<Real>::T2* sigeps,
                                                int nAtoms, int nsub, const SliceFinish& f, double* out, hipStream_t s);   // closed-form terms, sorted -> user order: out[nAtoms][nsub][2]
+// group sums of the completed table (atomenergy.hip, snb_evaluate_group_energies).  planGroups (host) packs the caller's CSR lists and the
+// work lists of the two mappings into one int array, uploaded once per call: [offStart] start[G + 1], [offAtoms] atoms, [offSmall] ids of the
+// groups of up to SNB_GROUP_SERIAL atoms, [offChunks] int4 (group, begin, end, 0) per chunk of a longer group, [offLarge] int4 (group,
+// first chunk, chunks, 0) per longer group; the int4 parts start at multiples of four ints.
+#define SNB_GROUP_SERIAL 32
+struct GroupPlan { int nGroups = 0, nSmall = 0, nChunks = 0, nLarge = 0, offStart = 0, offAtoms = 0, offSmall = 0, offChunks = 0, offLarge = 0; std::vector<int> packed; };
+void planGroups(int nGroups, const int32_t* start, GroupPlan& plan);      // (packed[offAtoms ...] is left for the caller to fill)
+template <typename Real> void launchGroupFinish(const double* tab, const int* userToSorted, const int* blockSubset, const typename Vec<Real>::T4* posq, const typename Vec<Real>::T2* sigeps,
+                                                int nsub, const SliceFinish& f, const GroupPlan& plan, const int* packed, double* partial /* [nChunks][nsub][2] */,
+                                                double* out /* [G][nsub][2] */, hipStream_t s);
 // per-atom forces by subset and term (atomforce.hip, snb_evaluate_atom_forces): tab = double [Npad][nsub][2][3] over the sorted index, added to
 template <typename Real> void launchAtomForcePairs(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, double* tab, hipStream_t s);
 template <typename Real> void launchAtomField(const PmeParams<Real>& p, double* tab, hipStream_t s);   // - q_i grad psi_J(r_i) from the unmixed real-space potentials of p
