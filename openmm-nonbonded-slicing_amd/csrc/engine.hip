@@ -1860,14 +1860,15 @@ public:
     // Per-atom interaction energies (snb_evaluate_atom_energies): the table A[i][J][t] of every atom with every subset.
     // Behaves as an energy-only step behaves -- current box and positions (a binding's posq through the same gather), the neighbour-list
     // rules of any execute, plain launches, no step graph, no timer -- and writes only the table: no force array, no force output, no bound
-    // buffer, neither the slice-energy partitions nor their sums.  Kernels: atomenergy.hip.  Reciprocal part: the UNMIXED pipeline with every
+    // buffer, neither the slice-energy partitions nor their sums.  Kernels: atomenergy.hip, atom_table.h.  Reciprocal part: the UNMIXED pipeline with every
     // mesh held (what a rank that owns all meshes runs), then the value part of the interpolation per (atom, mesh).
     // ------------------------------------------------------------------------------------------
     DevBuf<double> atomTab, atomOut;      // sorted-order working table [Npad][nsub][2]; user-order staging of a host result (both allocated at the first call)
-    // The pass that fills atomTab (sized by the caller, at least [Npad][nsub][2]) for the lists, box and positions in use: what
-    // snb_evaluate_atom_energies runs between the neighbour-list rules and its finish kernel, and the step of a group batch's frame.
-    void enqueueAtomPass(bool includeDirect, bool includeRecip) {
-        launchZeroFill(atomTab.p, sizeof(double) * (size_t)Npad * nsub * 2, stream);
+    // The pass that fills a per-atom table (tab, sized by the caller, at least [Npad][nsub][rowDoubles]) for the lists, box and positions in
+    // use: what snb_evaluate_atom_energies and snb_evaluate_atom_forces run between the neighbour-list rules and their finish kernels, and the
+    // step of a group batch's frame.  forces chooses the kernels only: the pair and stencil launchers of atomforce.hip, else of atomenergy.hip.
+    void enqueueAtomPass(bool includeDirect, bool includeRecip, double* tab, int rowDoubles, bool forces) {
+        launchZeroFill(tab, sizeof(double) * (size_t)Npad * nsub * rowDoubles, stream);
         // the position-gather pass of a step that clears nothing: sorted positions, the Coulomb-mesh cells, the displacement watch
         const bool recip = includeRecip && isPme() && nGrids > 0;
         GatherCells<Real> gc;
@@ -1895,34 +1896,45 @@ public:
             DirectParams<Real> p; PairListParams<Real> q;
             std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
             fillDirect(p); fillPairLists(q);
-            launchAtomPairs<Real>(p, methodClass(), wrapMode, &q, atomTab.p, stream);
+            if (forces) launchAtomForcePairs<Real>(p, methodClass(), wrapMode, &q, tab, stream);
+            else launchAtomPairs<Real>(p, methodClass(), wrapMode, &q, tab, stream);
         }
         if (recip) {
             PmeParams<Real> pp;
             std::memset(&pp, 0, sizeof(pp));
-            fillPme(pp, pme, false); pp.mix = 0;
-            runPmeFront(pp, stream);
-            launchAtomPotential<Real>(pp, atomTab.p, stream);
-            if (cfg.method == SNB_LJPME) {
-                fillPme(pp, dpme, false); pp.mix = 0;
+            auto mesh = [&](PmePlan<Real>& m) {      // the unmixed front of one mesh, then its part of every atom's row
+                fillPme(pp, m, false); pp.mix = 0;
                 runPmeFront(pp, stream);
-                launchAtomPotential<Real>(pp, atomTab.p, stream);
-            }
+                if (forces) launchAtomField<Real>(pp, tab, stream);
+                else launchAtomPotential<Real>(pp, tab, stream);
+            };
+            mesh(pme);
+            if (cfg.method == SNB_LJPME) mesh(dpme);
         }
     }
     // closed-form terms of a completed table row (the long-range dispersion correction is a per-slice constant: not attributed)
     SliceFinish makeAtomFinish(bool includeDirect, bool includeRecip) const { SliceFinish f = makeSliceFinish(includeDirect, includeRecip); f.dispCoef = nullptr; return f; }
+    // The refusals the three analysis entry points share, in the order they are raised.  args: the argument checks (outName == nullptr: the
+    // caller has checked its own outputs); state: what this engine cannot attribute to atoms.  snb_evaluate_group_energies checks its frame
+    // count between the two.
+    void refuseAtomCall(const std::string& who, const char* outName, const void* out, bool includeDirect, bool includeRecip, bool args, bool state) {
+        if (args) {
+            if (outName && !out) { err = who + ": " + outName + " is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+            if (!includeDirect && !includeRecip) { err = who + ": neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        }
+        if (state) {
+            if (cfg.shard_count > 1) { err = who + ": not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
+            if (cfg.method == SNB_Ewald && includeRecip) { err = who + ": the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        }
+    }
     void evaluateAtomEnergies(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
-        if (!out) { err = "snb_evaluate_atom_energies: atom_energies is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (!includeDirect && !includeRecip) { err = "snb_evaluate_atom_energies: neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (cfg.shard_count > 1) { err = "snb_evaluate_atom_energies: not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
-        if (cfg.method == SNB_Ewald && includeRecip) { err = "snb_evaluate_atom_energies: the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        refuseAtomCall("snb_evaluate_atom_energies", "atom_energies", out, includeDirect != 0, includeRecip != 0, true, true);
         beginExecute(false, includeRecip);
         const size_t tabN = (size_t)Npad * nsub * 2, outN = (size_t)N * nsub * 2;
         atomTab.resize(tabN);
         if (!outIsDevice) atomOut.resize(outN);
         double* const dst = outIsDevice ? out : atomOut.p;
-        enqueueAtomPass(includeDirect != 0, includeRecip != 0);
+        enqueueAtomPass(includeDirect != 0, includeRecip != 0, atomTab.p, 2, false);
         launchAtomFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, N, nsub, makeAtomFinish(includeDirect != 0, includeRecip != 0), dst, stream);
         endExecute();
         if (!outIsDevice) {
@@ -1952,10 +1964,9 @@ public:
             if (a < 0 || a >= N) { err = who + ": group " + std::to_string(g) + ": atom index " + std::to_string(a) + " is outside [0, " + std::to_string(N) + ")"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
         }
         const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
-        if (!direct && !recip) { err = who + ": neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        refuseAtomCall(who, nullptr, nullptr, direct, recip, true, false);
         if (b->n_frames < 0) { err = who + ": negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (cfg.shard_count > 1) { err = who + ": not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
-        if (cfg.method == SNB_Ewald && recip) { err = who + ": the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        refuseAtomCall(who, nullptr, nullptr, direct, recip, false, true);
         const int F = b->n_frames;
         if (F == 0) return;
         if (!b->positions && F != 1) { err = who + ": positions == NULL evaluates the engine's current state: n_frames must be 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
@@ -1987,7 +1998,7 @@ public:
             beginExecute(false, recip);
             prepare();
             atomTab.resize((size_t)Npad * nsub * 2);
-            enqueueAtomPass(direct, recip);
+            enqueueAtomPass(direct, recip, atomTab.p, 2, false);
             groupFinish(0);
             endExecute();
             deliver();
@@ -1998,7 +2009,7 @@ public:
             [&](int f) {
                 // (sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
                 atomTab.resize((size_t)std::max(Npad, npadPredict) * nsub * 2);
-                enqueueAtomPass(direct, recip);
+                enqueueAtomPass(direct, recip, atomTab.p, 2, false);
                 groupFinish(f);      // before evFrameStep[f & 1]: it reads userToSorted, blockSubset, posq and sigeps of this frame's list set
             },
             deliver);
@@ -2006,63 +2017,19 @@ public:
 
     // ------------------------------------------------------------------------------------------
     // Per-atom forces by partner subset and term (snb_evaluate_atom_forces): G[i][J][t] = -dE_raw[slice(s_i, J)][t]/dr_i.
-    // The frame, the refusals and the paths of evaluateAtomEnergies above, with the kernels of atomforce.hip: pair forces with every lambda 1
+    // The frame, the refusals and the pass of evaluateAtomEnergies above, with the kernels of atomforce.hip: pair forces with every lambda 1
     // into both ends' columns, the derivative part of the interpolation per (atom, held mesh) of the unmixed pipeline, no closed-form term
     // (none carries a force).  Writes only its table; working and staging tables are its own.
     // ------------------------------------------------------------------------------------------
     DevBuf<double> atomFTab, atomFOut;      // sorted-order working table [Npad][nsub][2][3]; user-order staging of a host result (both allocated at the first call)
     void evaluateAtomForces(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
-        if (!out) { err = "snb_evaluate_atom_forces: atom_forces is NULL"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (!includeDirect && !includeRecip) { err = "snb_evaluate_atom_forces: neither the direct nor the reciprocal part was asked for"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (cfg.shard_count > 1) { err = "snb_evaluate_atom_forces: not available on sharded engines (a rank holds a part of the lists and of the meshes)"; throw (int)SNB_ERR_UNSUPPORTED; }
-        if (cfg.method == SNB_Ewald && includeRecip) { err = "snb_evaluate_atom_forces: the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        refuseAtomCall("snb_evaluate_atom_forces", "atom_forces", out, includeDirect != 0, includeRecip != 0, true, true);
         beginExecute(false, includeRecip);
         const size_t tabN = (size_t)Npad * nsub * 6, outN = (size_t)N * nsub * 6;
         atomFTab.resize(tabN);
         if (!outIsDevice) atomFOut.resize(outN);
         double* const dst = outIsDevice ? out : atomFOut.p;
-        launchZeroFill(atomFTab.p, sizeof(double) * tabN, stream);
-        // the position-gather pass of a step that clears nothing: sorted positions, the Coulomb-mesh cells, the displacement watch
-        const bool recip = includeRecip && isPme() && nGrids > 0;
-        GatherCells<Real> gc;
-        std::memset(&gc, 0, sizeof(gc));
-        cellsFromGather = false; traceThisStep = false;
-        if (recip) {
-            PmeParams<Real> pp;
-            std::memset(&pp, 0, sizeof(pp));
-            fillPme(pp, pme, false);
-            if (pp.sortNcx > 0 && pp.colRange != nullptr) {
-                for (int i = 0; i < 9; i++) { gc.recip[i] = pp.recip[i]; gc.recipLo[i] = pp.recipLo[i]; }
-                gc.nx = pp.d.nx; gc.ny = pp.d.ny; gc.nz = pp.d.nz; gc.cells = pp.cells; gc.atomGrid = pp.atomGrid;
-                cellsFromGather = true;
-            }
-            if (dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
-        }
-        if (cfg.neighbor_padding > 0 && posRef.p) {
-            gc.posRef = posRef.p; gc.flags = dDispFlags;
-            const double half = 0.5 * cfg.neighbor_padding;
-            gc.fail2 = (Real)(half * half); gc.warn2 = (Real)(0.64 * half * half);
-        }
-        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream); }
-        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream);
-        if (includeDirect) {
-            DirectParams<Real> p; PairListParams<Real> q;
-            std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
-            fillDirect(p); fillPairLists(q);
-            launchAtomForcePairs<Real>(p, methodClass(), wrapMode, &q, atomFTab.p, stream);
-        }
-        if (recip) {
-            PmeParams<Real> pp;
-            std::memset(&pp, 0, sizeof(pp));
-            fillPme(pp, pme, false); pp.mix = 0;
-            runPmeFront(pp, stream);
-            launchAtomField<Real>(pp, atomFTab.p, stream);
-            if (cfg.method == SNB_LJPME) {
-                fillPme(pp, dpme, false); pp.mix = 0;
-                runPmeFront(pp, stream);
-                launchAtomField<Real>(pp, atomFTab.p, stream);
-            }
-        }
+        enqueueAtomPass(includeDirect != 0, includeRecip != 0, atomFTab.p, 6, true);
         launchAtomForceFinish(atomFTab.p, dUserToSorted.p, N, nsub, dst, stream);
         endExecute();
         if (!outIsDevice) {

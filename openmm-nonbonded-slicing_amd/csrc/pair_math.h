@@ -1,4 +1,4 @@
-// pair_math.h -- arithmetic helpers shared by the pair kernels (direct.hip) and the per-atom energy kernels (atomenergy.hip).
+// pair_math.h -- arithmetic helpers shared by the pair kernels (direct.hip) and the per-atom table kernels (atom_table.h, atomenergy.hip, atomforce.hip).
 #pragma once
 #include "snb_internal.h"
 

@@ -393,7 +393,7 @@ template <typename Real> __device__ inline void gridCoord(const Real* recip, con
 
 // ---------------------------------------------------------------------------------------------------
 // B-splines of order 5 and their derivatives (ReferencePME.cpp:264-317), in registers.  Shared by the PME kernels (pme.hip)
-// and the per-atom field kernel (atomforce.hip).
+// and the derivative form of the per-atom stencil kernel (k_atomStencil<.., GRAD = true>, atom_table.h).
 // ---------------------------------------------------------------------------------------------------
 template <typename Real> __device__ inline void bspline5(Real dr, Real* d, Real* dd) {
     d[4] = 0; d[1] = dr; d[0] = 1 - dr; d[2] = 0; d[3] = 0;
