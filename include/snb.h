@@ -385,6 +385,52 @@ typedef struct {
 } snb_group_batch;
 snb_status snb_evaluate_group_energies(snb_handle h, const snb_group_batch* b);
 
+/* -- per-group forces over stored frames, by subset and at lambda states ----------------------- */
+/* The same product for the force table: the table of snb_evaluate_atom_forces summed over lists of atoms (coarse-grained sites, a ligand,
+ * residues), for every frame of a stored trajectory, reduced on the device --
+ *     group_forces[f][g][J][t][d] = sum_{i in atoms(g)} G_f[i][J][t][d]
+ *     state_forces[f][k][g][d]    = sum_{i in atoms(g)} sum_J sum_t state_lambdas[k][slice(s_i, J)][t] G_f[i][J][t][d]
+ * with G_f the table of snb_evaluate_atom_forces at frame f: the same attribution, raw (lambda-independent) values, effective parameters,
+ * nothing added for the self term, the background or the dispersion correction.  state_forces is the net force on the group at lambda state
+ * k -- the force-matching target of a centre-of-mass site, the force on a ligand at every alchemical state from one evaluation per frame.
+ * The contraction is done per atom, before the group sum: s_i is the atom's own subset, and a group may span subsets.  n_states == 0: the
+ * raw rows alone.  n_states > 0: state_forces, and the raw rows as well unless group_forces is NULL; there is no cap on n_states.  Groups
+ * are lists as for snb_evaluate_group_energies: they may overlap, leave atoms out, be empty (zeros), and an index listed twice counts
+ * twice.  Every entry of every requested output is written.  The sums use no atomics: an output row is a function of the frame's table
+ * alone (the table itself is accumulated with double atomics).
+ * With frames given the call follows the contract of snb_evaluate_frames: everything is checked before anything is enqueued; the list of
+ * frame f + 1 is built beside the pass of frame f, or in line, by the same rules; host frames go through the pinned staging; host output
+ * costs one synchronisation, at the end; device output is complete in stream order; afterwards positions, box, lambdas and mask are the
+ * caller's and the next snb_execute rebuilds; no step graph is captured or updated; frame steps count in snb_stats.n_rebuilds and in no
+ * timer; snb_get_frame_stats counts the batch and its frames.  With positions == NULL (n_frames must be 1) it is ONE evaluation of the
+ * engine's current box and positions and behaves as snb_evaluate_atom_forces behaves, a bound context included.
+ * In both forms it writes ONLY its outputs: the forces (snb_get_forces), the buffer of snb_set_force_output, a binding's buffers and the
+ * engine's slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) stay bit for bit what they were.
+ * NULL batch, handle, group_start or group_atoms, group_forces NULL with n_states == 0, a negative n_states, n_states > 0 with NULL
+ * state_lambdas or state_forces, n_groups < 1, a group_start that does not begin at 0 or decreases, an atom index outside [0, n_atoms)
+ * (snb_last_error names the group), both include flags 0, a negative n_frames, positions == NULL with n_frames != 1:
+ * SNB_ERR_INVALID_ARGUMENT.  shard_count > 1, SNB_Ewald with include_reciprocal: SNB_ERR_UNSUPPORTED.  n_frames == 0 (after these checks):
+ * SNB_OK, no work.  Frames given while a context is bound: SNB_ERR_STATE.  Box errors: as snb_evaluate_frames, with the frame index.  The
+ * working memory (the table over the sorted atoms, shared with snb_evaluate_atom_forces; the chunk sums) is allocated at the first call. */
+typedef struct {
+    int32_t        n_frames;
+    const void*    positions;        /* as snb_group_batch: [F][N][3] or [F][N][4]; NULL: the engine's CURRENT box and positions (n_frames must be 1) */
+    int32_t        is_device;
+    int32_t        is_double;
+    int32_t        stride4;
+    const double*  boxes;            /* HOST [F][9], reduced form, or NULL: the engine's current box for every frame */
+    int32_t        include_direct, include_reciprocal;
+    int32_t        n_groups;         /* G >= 1 */
+    const int32_t* group_start;      /* HOST [G + 1], group_start[0] == 0, non-decreasing */
+    const int32_t* group_atoms;      /* HOST [group_start[G]], USER atom indices */
+    double*        group_forces;     /* [F][G][n_subsets][2][3] raw (Coulomb, vdW) x (x, y, z), kJ/mol/nm; may be NULL when n_states > 0 */
+    int32_t        out_is_device;
+    int32_t        n_states;         /* K >= 0 lambda states */
+    const double*  state_lambdas;    /* HOST [K][S][2] */
+    double*        state_forces;     /* [F][K][G][3]; same residence as group_forces */
+} snb_group_force_batch;
+snb_status snb_evaluate_group_forces(snb_handle h, const snb_group_force_batch* b);
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

@@ -20,7 +20,7 @@ SYMBOLS = [
     "snb_rebuild_neighbors", "snb_execute", "snb_get_forces", "snb_set_force_output", "snb_set_shard_blocks", "snb_get_slice_energies", "snb_slice_energies_device", "snb_synchronize",
     "snb_get_pme_parameters", "snb_get_ljpme_parameters", "snb_get_stats", "snb_reset_timers", "snb_set_timing_interval", "snb_legal_grid_size", "snb_abi_version",
     "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed", "snb_evaluate_frames", "snb_get_frame_stats", "snb_evaluate_atom_energies",
-    "snb_evaluate_atom_forces", "snb_evaluate_group_energies",
+    "snb_evaluate_atom_forces", "snb_evaluate_group_energies", "snb_evaluate_group_forces",
 ]
 
 SNB_OK, SNB_ERR_INVALID_ARGUMENT, SNB_ERR_HIP, SNB_ERR_BOX_TOO_SMALL, SNB_ERR_NOT_PME, SNB_ERR_STATE, SNB_ERR_UNSUPPORTED = range(7)
@@ -75,6 +75,18 @@ class SnbGroupBatch(ctypes.Structure):
         ("stride4", ctypes.c_int32), ("boxes", ctypes.POINTER(ctypes.c_double)), ("include_direct", ctypes.c_int32), ("include_reciprocal", ctypes.c_int32),
         ("n_groups", ctypes.c_int32), ("group_start", ctypes.POINTER(ctypes.c_int32)), ("group_atoms", ctypes.POINTER(ctypes.c_int32)),
         ("group_energies", ctypes.c_void_p), ("out_is_device", ctypes.c_int32),
+    ]
+
+
+class SnbGroupForceBatch(ctypes.Structure):
+    """snb_group_force_batch: groups of atoms over F stored frames (or the current state), raw rows and K lambda states, for
+    snb_evaluate_group_forces (include/snb.h)."""
+    _fields_ = [
+        ("n_frames", ctypes.c_int32), ("positions", ctypes.c_void_p), ("is_device", ctypes.c_int32), ("is_double", ctypes.c_int32),
+        ("stride4", ctypes.c_int32), ("boxes", ctypes.POINTER(ctypes.c_double)), ("include_direct", ctypes.c_int32), ("include_reciprocal", ctypes.c_int32),
+        ("n_groups", ctypes.c_int32), ("group_start", ctypes.POINTER(ctypes.c_int32)), ("group_atoms", ctypes.POINTER(ctypes.c_int32)),
+        ("group_forces", ctypes.c_void_p), ("out_is_device", ctypes.c_int32), ("n_states", ctypes.c_int32),
+        ("state_lambdas", ctypes.POINTER(ctypes.c_double)), ("state_forces", ctypes.c_void_p),
     ]
 
 
@@ -146,6 +158,7 @@ def lib():
     L.snb_evaluate_atom_energies.argtypes = [vp, i32, i32, vp, i32]      # (the table as an address: host or device by out_is_device)
     L.snb_evaluate_atom_forces.argtypes = [vp, i32, i32, vp, i32]        # (the same)
     L.snb_evaluate_group_energies.argtypes = [vp, ctypes.POINTER(SnbGroupBatch)]
+    L.snb_evaluate_group_forces.argtypes = [vp, ctypes.POINTER(SnbGroupForceBatch)]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError if the header and the library ever diverge
     _lib = L

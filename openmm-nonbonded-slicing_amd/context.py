@@ -390,23 +390,19 @@ class HipCalcSlicedNonbondedForceKernel:
         """Sums of a per-atom force table over lists of atom indices, one list per group (residue, molecule): (G, n_subsets, 2, 3)."""
         return HipCalcSlicedNonbondedForceKernel.groupAtomEnergies(table, groups)      # (the reduction does not depend on the entry's shape)
 
-    def computeSliceEnergiesForFrames(self, context, positions=None, boxes=None, slices=None, lambdaStates=None, positionsDevicePointer=None, numFrames=None):
-        """Raw per-slice energies [F][S][2] of F stored frames in one call (include/snb.h, snb_evaluate_frames): the loop of an MBAR or
-        reweighting pass over a trajectory, pipelined inside the engine -- the list of the next frame is built beside the step of this one.
-        positions: NumPy [F][N][3], float32 or float64 (host).  Frames already on the device: positionsDevicePointer=(address, isDouble) of
-        a contiguous [F][N][3] array on the engine's device, with numFrames.  boxes: [F][3][3] (or [F][9]) reduced box vectors per frame;
-        None: the context's box for every frame.  slices: as in computeSliceEnergies -- only those are evaluated, the other rows are NaN.
-        lambdaStates: [K][S][2]; then the result is (sliceEnergies, stateEnergies[F][K]), stateEnergies[f][k] = sum lambdaStates[k] *
-        sliceEnergies[f], summed on the device (every slice must be evaluated: not with slices).  Parameters and lambdas are pushed from the
-        context first; the context's own positions, the forces of the last forces step and the derivative mask stay as they are."""
+    def _push_frame_state(self, context):
+        """What a ...ForFrames call pushes from the context first: parameters, lambdas and the box (the frames bring the positions)."""
         self._push_parameters(context.getParameters())
         box = np.ascontiguousarray(context.getPeriodicBoxVectors(), dtype=np.float64).reshape(9)
         self._check(self._lib.snb_set_box(self._h, _dp(box)))
-        S = self.numSlices
-        b = _capi.SnbFrameBatch()
+
+    def _frames_into(self, b, who, positions, boxes, positionsDevicePointer, numFrames):
+        """The frames arguments the ...ForFrames methods share, written into the batch b (n_frames, positions, is_device, is_double,
+        stride4, boxes).  Returns (F, the arrays b points into: the caller keeps them until the call has returned)."""
+        keep = []
         if positionsDevicePointer is not None:
             if positions is not None or numFrames is None:
-                raise OpenMMException("computeSliceEnergiesForFrames: positionsDevicePointer goes with numFrames and without positions")
+                raise OpenMMException("%s: positionsDevicePointer goes with numFrames and without positions" % who)
             ptr, isDouble = positionsDevicePointer
             F = int(numFrames)
             b.positions = ctypes.c_void_p(int(ptr)); b.is_device = 1; b.is_double = int(bool(isDouble))
@@ -416,15 +412,32 @@ class HipCalcSlicedNonbondedForceKernel:
                 pos = pos.astype(np.float64, copy=False)
             pos = np.ascontiguousarray(pos)
             if pos.ndim != 3 or pos.shape[1:] != (self.numParticles, 3):
-                raise OpenMMException("computeSliceEnergiesForFrames: positions must be [F][%d][3]" % self.numParticles)
+                raise OpenMMException("%s: positions must be [F][%d][3]" % (who, self.numParticles))
             F = pos.shape[0]
+            keep.append(pos)
             b.positions = pos.ctypes.data_as(ctypes.c_void_p); b.is_device = 0; b.is_double = int(pos.dtype == np.float64)
         b.n_frames = F; b.stride4 = 0
         if boxes is not None:
             bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 9))
             if bx.shape[0] != F:
-                raise OpenMMException("computeSliceEnergiesForFrames: one box per frame")
+                raise OpenMMException("%s: one box per frame" % who)
+            keep.append(bx)
             b.boxes = _dp(bx)
+        return F, keep
+
+    def computeSliceEnergiesForFrames(self, context, positions=None, boxes=None, slices=None, lambdaStates=None, positionsDevicePointer=None, numFrames=None):
+        """Raw per-slice energies [F][S][2] of F stored frames in one call (include/snb.h, snb_evaluate_frames): the loop of an MBAR or
+        reweighting pass over a trajectory, pipelined inside the engine -- the list of the next frame is built beside the step of this one.
+        positions: NumPy [F][N][3], float32 or float64 (host).  Frames already on the device: positionsDevicePointer=(address, isDouble) of
+        a contiguous [F][N][3] array on the engine's device, with numFrames.  boxes: [F][3][3] (or [F][9]) reduced box vectors per frame;
+        None: the context's box for every frame.  slices: as in computeSliceEnergies -- only those are evaluated, the other rows are NaN.
+        lambdaStates: [K][S][2]; then the result is (sliceEnergies, stateEnergies[F][K]), stateEnergies[f][k] = sum lambdaStates[k] *
+        sliceEnergies[f], summed on the device (every slice must be evaluated: not with slices).  Parameters and lambdas are pushed from the
+        context first; the context's own positions, the forces of the last forces step and the derivative mask stay as they are."""
+        self._push_frame_state(context)
+        S = self.numSlices
+        b = _capi.SnbFrameBatch()
+        F, keep = self._frames_into(b, "computeSliceEnergiesForFrames", positions, boxes, positionsDevicePointer, numFrames)
         b.mode = 1 if slices is None else 2
         b.include_direct = 1; b.include_reciprocal = 1
         out = np.zeros((F, S, 2))
@@ -458,11 +471,11 @@ class HipCalcSlicedNonbondedForceKernel:
         atoms = np.concatenate(lists).astype(np.int32) if start[-1] > 0 else np.zeros(0, dtype=np.int32)
         return start, np.ascontiguousarray(atoms)
 
-    def _groupBatch(self, groups, includeDirect, includeReciprocal):
+    def _groupBatch(self, groups, includeDirect, includeReciprocal, batch=_capi.SnbGroupBatch):
         start, atoms = self.groupsToCSR(groups)
         if len(start) < 2:
-            raise OpenMMException("group energies: at least one group")
-        b = _capi.SnbGroupBatch()
+            raise OpenMMException("group energies and forces: at least one group")
+        b = batch()
         if len(atoms) == 0:
             atoms = np.zeros(1, dtype=np.int32)      # (only empty groups: group_atoms must still be an address)
         b.n_groups = len(start) - 1; b.group_start = _ip(start); b.group_atoms = _ip(atoms)
@@ -496,33 +509,11 @@ class HipCalcSlicedNonbondedForceKernel:
         in computeSliceEnergiesForFrames.  devicePointer: address of a double [F][G][n_subsets][2] array on the engine's device that takes
         the result (complete in stream order); then None is returned.  Parameters are pushed from the context first; the context's own
         positions, the forces and the slice energies of the last steps stay as they are."""
-        self._push_parameters(context.getParameters())
-        box = np.ascontiguousarray(context.getPeriodicBoxVectors(), dtype=np.float64).reshape(9)
-        self._check(self._lib.snb_set_box(self._h, _dp(box)))
+        self._push_frame_state(context)
         b, keep = self._groupBatch(groups, includeDirect, includeReciprocal)
-        if positionsDevicePointer is not None:
-            if positions is not None or numFrames is None:
-                raise OpenMMException("computeGroupEnergiesForFrames: positionsDevicePointer goes with numFrames and without positions")
-            ptr, isDouble = positionsDevicePointer
-            F = int(numFrames)
-            b.positions = ctypes.c_void_p(int(ptr)); b.is_device = 1; b.is_double = int(bool(isDouble))
-        else:
-            if positions is None:
-                raise OpenMMException("computeGroupEnergiesForFrames: positions or positionsDevicePointer must be given (computeGroupEnergies evaluates the context's own state)")
-            pos = np.asarray(positions)
-            if pos.dtype != np.float32:
-                pos = pos.astype(np.float64, copy=False)
-            pos = np.ascontiguousarray(pos)
-            if pos.ndim != 3 or pos.shape[1:] != (self.numParticles, 3):
-                raise OpenMMException("computeGroupEnergiesForFrames: positions must be [F][%d][3]" % self.numParticles)
-            F = pos.shape[0]
-            b.positions = pos.ctypes.data_as(ctypes.c_void_p); b.is_device = 0; b.is_double = int(pos.dtype == np.float64)
-        b.n_frames = F; b.stride4 = 0
-        if boxes is not None:
-            bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 9))
-            if bx.shape[0] != F:
-                raise OpenMMException("computeGroupEnergiesForFrames: one box per frame")
-            b.boxes = _dp(bx)
+        if positions is None and positionsDevicePointer is None:
+            raise OpenMMException("computeGroupEnergiesForFrames: positions or positionsDevicePointer must be given (computeGroupEnergies evaluates the context's own state)")
+        F, frames = self._frames_into(b, "computeGroupEnergiesForFrames", positions, boxes, positionsDevicePointer, numFrames)
         out = None
         if devicePointer is not None:
             b.group_energies = ctypes.c_void_p(int(devicePointer)); b.out_is_device = 1
@@ -530,6 +521,75 @@ class HipCalcSlicedNonbondedForceKernel:
             out = np.zeros((F, b.n_groups, self.numSubsets, 2))
             b.group_energies = out.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
         self._check(self._lib.snb_evaluate_group_energies(self._h, ctypes.byref(b)))
+        return out
+
+    def _groupForceOutputs(self, b, F, lambdaStates, keep):
+        """Host outputs of a group-force batch: rows (F, G, n_subsets, 2, 3) and, with lambdaStates [K][S][2], stateForces (F, K, G, 3)."""
+        rows = np.zeros((F, b.n_groups, self.numSubsets, 2, 3))
+        b.group_forces = rows.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        states = None
+        if lambdaStates is not None:
+            lam = np.ascontiguousarray(np.asarray(lambdaStates, dtype=np.float64).reshape(-1, self.numSlices, 2))
+            keep.append(lam)
+            states = np.zeros((F, lam.shape[0], b.n_groups, 3))
+            b.n_states = lam.shape[0]; b.state_lambdas = _dp(lam); b.state_forces = states.ctypes.data_as(ctypes.c_void_p)
+        return rows, states
+
+    def computeGroupForces(self, context, groups, includeDirect=True, includeReciprocal=True, lambdaStates=None, devicePointer=None):
+        """Per-group forces by partner subset and term at the context's positions, box and parameters (include/snb.h,
+        snb_evaluate_group_forces with positions == NULL): the table of computeAtomForces summed over each list of atom indices in
+        ``groups`` on the device, (G, n_subsets, 2, 3) -- what groupAtomForces(computeAtomForces(...), groups) gives, without the per-atom
+        table crossing to the host.  lambdaStates [K][S][2]: then the result is (rows, stateForces (K, G, 3)), the net force on every group
+        at every lambda state (groupForcesAtStates of the table).  devicePointer: address of a double [G][n_subsets][2][3] array on the
+        engine's device that takes the rows -- with lambdaStates a pair (rows address or None, address of a double [K][G][3] array) --
+        complete in stream order; then None is returned."""
+        self._push_state(context)
+        b, keep = self._groupBatch(groups, includeDirect, includeReciprocal, _capi.SnbGroupForceBatch)
+        keep = list(keep)
+        b.n_frames = 1
+        if devicePointer is None:
+            rows, states = self._groupForceOutputs(b, 1, lambdaStates, keep)
+            self._check(self._lib.snb_evaluate_group_forces(self._h, ctypes.byref(b)))
+            return rows[0] if states is None else (rows[0], states[0])
+        b.out_is_device = 1
+        if lambdaStates is None:
+            b.group_forces = ctypes.c_void_p(int(devicePointer))
+        else:
+            rowsPtr, statesPtr = devicePointer
+            lam = np.ascontiguousarray(np.asarray(lambdaStates, dtype=np.float64).reshape(-1, self.numSlices, 2))
+            b.group_forces = ctypes.c_void_p(int(rowsPtr)) if rowsPtr is not None else None
+            b.n_states = lam.shape[0]; b.state_lambdas = _dp(lam); b.state_forces = ctypes.c_void_p(int(statesPtr))
+        self._check(self._lib.snb_evaluate_group_forces(self._h, ctypes.byref(b)))
+        return None
+
+    def computeGroupForcesForFrames(self, context, groups, positions=None, boxes=None, includeDirect=True, includeReciprocal=True, lambdaStates=None,
+                                    positionsDevicePointer=None, numFrames=None):
+        """Per-group forces [F][G][n_subsets][2][3] of F stored frames in one call (include/snb.h, snb_evaluate_group_forces): the force
+        every subset puts on every coarse-grained site or ligand frame by frame -- mean-force decomposition and force matching over a
+        trajectory -- through the frame pipeline of computeSliceEnergiesForFrames with the atom-force pass as its step and the sum over
+        each group's atoms on the device.  groups: a list of lists of atom indices, as in groupAtomForces.  positions, boxes,
+        positionsDevicePointer, numFrames: as in computeSliceEnergiesForFrames.  lambdaStates [K][S][2]: then the result is (rows,
+        stateForces (F, K, G, 3)), the net force on every group at every lambda state, contracted per atom on the device.  Parameters
+        are pushed from the context first; the context's own positions, the forces and the slice energies of the last steps stay as they
+        are."""
+        self._push_frame_state(context)
+        b, keep = self._groupBatch(groups, includeDirect, includeReciprocal, _capi.SnbGroupForceBatch)
+        if positions is None and positionsDevicePointer is None:
+            raise OpenMMException("computeGroupForcesForFrames: positions or positionsDevicePointer must be given (computeGroupForces evaluates the context's own state)")
+        F, frames = self._frames_into(b, "computeGroupForcesForFrames", positions, boxes, positionsDevicePointer, numFrames)
+        rows, states = self._groupForceOutputs(b, F, lambdaStates, frames)
+        self._check(self._lib.snb_evaluate_group_forces(self._h, ctypes.byref(b)))
+        return rows if states is None else (rows, states)
+
+    @staticmethod
+    def groupForcesAtStates(table, subsets, groups, lambdaStates):
+        """The net force (K, G, 3) on every group at every lambda state a per-atom force table implies -- the NumPy statement of
+        state_forces: forcesFromAtomForces per state, then the sum over each group's atoms."""
+        K = HipCalcSlicedNonbondedForceKernel
+        lam = np.asarray(lambdaStates, dtype=np.float64)
+        out = np.zeros((lam.shape[0], len(groups), 3))
+        for k in range(lam.shape[0]):
+            out[k] = K.groupAtomEnergies(K.forcesFromAtomForces(table, subsets, lam[k]), groups)
         return out
 
     def getFrameStats(self):
@@ -642,6 +702,9 @@ class SlicedNonbondedForceImpl:
     def getGroupEnergies(self, context, groups, **options):
         return self.kernel.computeGroupEnergies(context, groups, **options)
 
+    def getGroupForces(self, context, groups, **options):
+        return self.kernel.computeGroupForces(context, groups, **options)
+
 
 class System:
     def __init__(self):
@@ -746,6 +809,16 @@ class Context:
         for impl in self._impls:
             if impl.owner is force:
                 return impl.getGroupEnergies(self, groups, **options)
+        raise OpenMMException("force not in this context")
+
+    def getGroupForces(self, force, groups, **options):
+        """Per-group forces of ``force`` by partner subset and term, (G, n_subsets, 2, 3), with lambdaStates also (K, G, 3):
+        HipCalcSlicedNonbondedForceKernel.computeGroupForces."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        for impl in self._impls:
+            if impl.owner is force:
+                return impl.getGroupForces(self, groups, **options)
         raise OpenMMException("force not in this context")
 
     def getAtomForces(self, force, **options):

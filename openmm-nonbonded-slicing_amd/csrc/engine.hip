@@ -116,6 +116,7 @@ struct EngineBase {
     virtual void evaluateAtomEnergies(int, int, double*, int) = 0;
     virtual void evaluateAtomForces(int, int, double*, int) = 0;
     virtual void evaluateGroupEnergies(const snb_group_batch*) = 0;
+    virtual void evaluateGroupForces(const snb_group_force_batch*) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
@@ -1915,7 +1916,7 @@ public:
     // closed-form terms of a completed table row (the long-range dispersion correction is a per-slice constant: not attributed)
     SliceFinish makeAtomFinish(bool includeDirect, bool includeRecip) const { SliceFinish f = makeSliceFinish(includeDirect, includeRecip); f.dispCoef = nullptr; return f; }
     // The refusals the three analysis entry points share, in the order they are raised.  args: the argument checks (outName == nullptr: the
-    // caller has checked its own outputs); state: what this engine cannot attribute to atoms.  snb_evaluate_group_energies checks its frame
+    // caller has checked its own outputs); state: what this engine cannot attribute to atoms.  The group calls (checkGroupCall) check their frame
     // count between the two.
     void refuseAtomCall(const std::string& who, const char* outName, const void* out, bool includeDirect, bool includeRecip, bool args, bool state) {
         if (args) {
@@ -1950,29 +1951,34 @@ public:
     // the chunk sums and the staging of a host result are its own (atomTab is shared with evaluateAtomEnergies, which refills it).
     // ------------------------------------------------------------------------------------------
     DevBuf<int> dGroupPlan; DevBuf<double> groupPartial, groupOut;
-    void evaluateGroupEnergies(const snb_group_batch* b) override {
-        const auto t0 = std::chrono::steady_clock::now();
-        const std::string who = "snb_evaluate_group_energies";
-        // ---- everything is checked before anything is enqueued or changed
-        if (!b->group_energies || !b->group_start || !b->group_atoms) { err = who + ": group_energies, group_start and group_atoms must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        const int G = b->n_groups;
+    // What snb_evaluate_group_energies and snb_evaluate_group_forces check, in the order it is raised -- everything before anything is
+    // enqueued or changed.  outputs: whether the caller's outputs are as they must be (else the message names outputNames).  Returns
+    // whether there is work (false: n_frames == 0).
+    bool checkGroupCall(const FrameInput& in, bool outputs, const char* outputNames, int G, const int32_t* start, const int32_t* atoms, bool direct, bool recip) {
+        const std::string who = in.who;
+        if (!outputs || !start || !atoms) { err = who + ": " + outputNames + ", group_start and group_atoms must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
         if (G < 1) { err = who + ": n_groups must be at least 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (b->group_start[0] != 0) { err = who + ": group_start[0] must be 0"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        for (int g = 0; g < G; g++) if (b->group_start[g + 1] < b->group_start[g]) { err = who + ": group_start decreases at group " + std::to_string(g); throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        for (int g = 0; g < G; g++) for (int e = b->group_start[g]; e < b->group_start[g + 1]; e++) {
-            const int a = b->group_atoms[e];
+        if (start[0] != 0) { err = who + ": group_start[0] must be 0"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        for (int g = 0; g < G; g++) if (start[g + 1] < start[g]) { err = who + ": group_start decreases at group " + std::to_string(g); throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        for (int g = 0; g < G; g++) for (int e = start[g]; e < start[g + 1]; e++) {
+            const int a = atoms[e];
             if (a < 0 || a >= N) { err = who + ": group " + std::to_string(g) + ": atom index " + std::to_string(a) + " is outside [0, " + std::to_string(N) + ")"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
         }
-        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
         refuseAtomCall(who, nullptr, nullptr, direct, recip, true, false);
-        if (b->n_frames < 0) { err = who + ": negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (in.F < 0) { err = who + ": negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
         refuseAtomCall(who, nullptr, nullptr, direct, recip, false, true);
-        const int F = b->n_frames;
-        if (F == 0) return;
-        if (!b->positions && F != 1) { err = who + ": positions == NULL evaluates the engine's current state: n_frames must be 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-        if (b->positions && ctx.on) { err = who + ": frames were given while a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        if (in.F == 0) return false;
+        if (!in.positions && in.F != 1) { err = who + ": positions == NULL evaluates the engine's current state: n_frames must be 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (in.positions && ctx.on) { err = who + ": frames were given while a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        if (in.positions) checkFrames(in, recip);
+        return true;
+    }
+    void evaluateGroupEnergies(const snb_group_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int G = b->n_groups, F = b->n_frames;
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
         const FrameInput in{"snb_evaluate_group_energies", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
-        if (b->positions) checkFrames(in, recip);
+        if (!checkGroupCall(in, b->group_energies != nullptr, "group_energies", G, b->group_start, b->group_atoms, direct, recip)) return;
         // ---- the lists, packed with the work lists of the two mappings: one upload per call, through the pinned ring
         GroupPlan plan;
         planGroups(G, b->group_start, plan);
@@ -2036,6 +2042,68 @@ public:
             HIPCHECK(hipMemcpyAsync(out, atomFOut.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
             HIPCHECK(hipStreamSynchronize(stream));
         }
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Per-group forces over stored frames, by subset and at lambda states (snb_evaluate_group_forces): the force
+    // table summed over lists of atoms on the device, per frame, and contracted per atom with K lambda states.  evaluateGroupEnergies with
+    // the force pass as the step and the group-force finish of atomforce.hip.  Writes only its outputs: the chunk sums, the device copy of
+    // the states and the staging of a host result are its own (atomFTab is shared with evaluateAtomForces, which refills it; the plan's
+    // buffer with evaluateGroupEnergies, which uploads its own).
+    // ------------------------------------------------------------------------------------------
+    DevBuf<double> groupFPartial, groupFOut, groupFStates, dGroupLambdas;
+    void evaluateGroupForces(const snb_group_force_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int G = b->n_groups, F = b->n_frames, K = b->n_states;
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
+        const FrameInput in{"snb_evaluate_group_forces", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
+        if (K < 0) { err = std::string(in.who) + ": negative state count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const bool outputs = K > 0 ? (b->state_lambdas && b->state_forces) : b->group_forces != nullptr;
+        if (!checkGroupCall(in, outputs, K > 0 ? "state_lambdas and state_forces" : "group_forces", G, b->group_start, b->group_atoms, direct, recip)) return;
+        // ---- the lists, packed with the work lists of the two mappings, and the states: one upload each per call, through the pinned ring
+        GroupPlan plan;
+        planGroups(G, b->group_start, plan);
+        std::copy(b->group_atoms, b->group_atoms + b->group_start[G], plan.packed.begin() + plan.offAtoms);
+        const bool wantRows = b->group_forces != nullptr, hostOut = b->out_is_device == 0;
+        const size_t rowLen = (size_t)G * nsub * 6, stateLen = (size_t)K * G * 3;
+        double* rows = b->group_forces; double* states = b->state_forces;
+        auto prepare = [&]() {
+            pinned.upload(dGroupPlan, plan.packed, stream);
+            if (K > 0) pinned.upload(dGroupLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * S * 2), stream);
+            groupFPartial.resize((size_t)std::max(plan.nChunks, 1) * ((wantRows ? (size_t)nsub * 6 : 0) + (size_t)K * 3));
+            if (hostOut && wantRows) { groupFOut.resize((size_t)F * rowLen); rows = groupFOut.p; }
+            if (hostOut && K > 0) { groupFStates.resize((size_t)F * stateLen); states = groupFStates.p; }
+        };
+        auto groupFinish = [&](int f) {
+            launchGroupForceFinish(atomFTab.p, dUserToSorted.p, blockSubset.p, nsub, plan, dGroupPlan.p, dGroupLambdas.p, K, groupFPartial.p, wantRows ? rows + (size_t)f * rowLen : nullptr,
+                                   K > 0 ? states + (size_t)f * stateLen : nullptr, stream);
+        };
+        auto deliver = [&]() {
+            if (!hostOut) return false;
+            if (wantRows) HIPCHECK(hipMemcpyAsync(b->group_forces, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+            if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_forces, states, sizeof(double) * (size_t)F * stateLen, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+            return true;
+        };
+        if (!b->positions) {      // the engine's current state, as snb_evaluate_atom_forces takes it
+            beginExecute(false, recip);
+            prepare();
+            atomFTab.resize((size_t)Npad * nsub * 6);
+            enqueueAtomPass(direct, recip, atomFTab.p, 6, true);
+            groupFinish(0);
+            endExecute();
+            deliver();
+            return;
+        }
+        prepare();
+        runFrames(in, t0,
+            [&](int f) {
+                // (sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
+                atomFTab.resize((size_t)std::max(Npad, npadPredict) * nsub * 6);
+                enqueueAtomPass(direct, recip, atomFTab.p, 6, true);
+                groupFinish(f);      // before evFrameStep[f & 1]: it reads userToSorted and blockSubset of this frame's list set
+            },
+            deliver);
     }
 
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
@@ -2284,6 +2352,10 @@ snb_status snb_evaluate_atom_forces(snb_handle h, int32_t includeDirect, int32_t
 snb_status snb_evaluate_group_energies(snb_handle h, const snb_group_batch* b) {
     if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_energies: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
     return guard(h, [&] { h->impl->evaluateGroupEnergies(b); });
+}
+snb_status snb_evaluate_group_forces(snb_handle h, const snb_group_force_batch* b) {
+    if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_forces: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
+    return guard(h, [&] { h->impl->evaluateGroupForces(b); });
 }
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 

@@ -343,6 +343,10 @@ template <typename Real> void launchGroupFinish(const double* tab, const int* us
 template <typename Real> void launchAtomForcePairs(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, double* tab, hipStream_t s);
 template <typename Real> void launchAtomField(const PmeParams<Real>& p, double* tab, hipStream_t s);   // - q_i grad psi_J(r_i) from the unmixed real-space potentials of p
 void launchAtomForceFinish(const double* tab, const int* userToSorted, int nAtoms, int nsub, double* out, hipStream_t s);   // sorted -> user order: out[nAtoms][nsub][2][3]
+// group sums of the force table (atomforce.hip, snb_evaluate_group_forces), over the plan of planGroups: rows[G][nsub][2][3] (nullptr: not
+// asked for) and, with nStates > 0, states[nStates][G][3] = the rows contracted per atom with stateLambdas[nStates][S][2] (device)
+void launchGroupForceFinish(const double* tab, const int* userToSorted, const int* blockSubset, int nsub, const GroupPlan& plan, const int* packed, const double* stateLambdas, int nStates,
+                            double* partial /* [nChunks][(rows ? nsub * 6 : 0) + nStates * 3] */, double* rows, double* states, hipStream_t s);
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s);   // 1: forward z FFT already done; 2: ... and the spectrum is plane-major (plane path)
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s);   // rebuild time: fills the plane path's kernel-value table
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s);   // after a spreader that returned 2: k_planeXY + k_fftZInvMix instead of forward FFT, convolution, inverse FFT
