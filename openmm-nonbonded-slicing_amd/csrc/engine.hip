@@ -46,6 +46,14 @@ struct HipError { std::string msg; };
         if (e_ != hipSuccess) throw HipError{std::string(#expr) + ": " + hipGetErrorString(e_)};               \
     } while (0)
 
+// runs f when the scope is left, by return or by exception: host state that a call borrows and must put back (f makes no HIP call)
+template <typename F> struct ScopeExit {
+    F f;
+    explicit ScopeExit(F g) : f(std::move(g)) {}
+    ScopeExit(const ScopeExit&) = delete;
+    ~ScopeExit() { f(); }
+};
+
 template <typename T> struct DevBuf {
     T* p = nullptr; size_t n = 0;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -113,8 +121,7 @@ struct EngineBase {
     virtual void setTimingInterval(int) = 0;
     virtual void getPme(double*, int32_t*, bool dispersion) = 0;
     virtual void evaluateFrames(const snb_frame_batch*) = 0;
-    virtual void evaluateAtomEnergies(int, int, double*, int) = 0;
-    virtual void evaluateAtomForces(int, int, double*, int) = 0;
+    virtual void evaluateAtomTable(bool forces, int, int, double*, int) = 0;
     virtual void evaluateGroupEnergies(const snb_group_batch*) = 0;
     virtual void evaluateGroupForces(const snb_group_force_batch*) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
@@ -287,11 +294,10 @@ public:
     // staging buffers on a copy stream, ahead of their build.  evFrameStep[f & 1] follows the step of frame f: whatever rewrites something
     // that step read (the shadow set, a staging slot) waits for it on its own stream -- the host never drains the step stream between frames.
     snb_frame_stats fstats;
-    double* frameRow = nullptr;      // the row of the caller's table the step's finish kernel also writes (null outside a batch)
     bool plainSort = false;      // frame builds issue phase A as plain launches: every frame is another position pointer, i.e. another graph key
     hipStream_t streamCopy = nullptr; hipEvent_t evFrameStep[2] = {nullptr, nullptr}, evFrameUp[2] = {nullptr, nullptr}, evBatchStart = nullptr; bool frameUpPending[2] = {false, false};
     void* framePinned[2] = {nullptr, nullptr}; size_t framePinnedCap[2] = {0, 0}; DevBuf<unsigned char> frameDev[2];
-    DevBuf<double> frameRows, frameStates, dStateLambdas;
+    DevBuf<double> frameTab, frameStates, dStateLambdas;
     bool sideBuilding = false, sidePending = false; int sideSeq = 0; long long sideBuilds = 0, sideDiscarded = 0;
     int lastPadCount = 0;      // the exact padded count of the last accepted build (what a frame batch sizes its own prediction from)
     int npadPredict = 0; long long padMispredictions = 0;      // > 0: size of the padded arrays the next GPU rebuild assumes (gpuRebuild); how often that was too small
@@ -348,8 +354,6 @@ public:
     DevBuf<int> pmeCells, dZIndex, dScanA, dScanB, dScanC, dAtomCell, dExtent;
     double tileCell[9] = {0};      // the cell the tile image codes refer to (the box; an enclosing cell for CutoffNonPeriodic)
     DevBuf<long long> dNbTrace, dPmeTrace, dStepTrace;      // dStepTrace: SNB_STEP_TRACE, device wall-clock stamps of the last replayed step
-    bool cellsFromGather = false;   // this step's gather pass already wrote the Coulomb-mesh cells
-    bool traceThisStep = false;
     // Parameter offsets on the device (the reference: platforms/common/src/kernels/nonbondedParameters.cc:4-179).  charge/sigma/epsilon
     // and the exception arrays above hold the BASE values; effective = base + sum_k global[k] * delta is formed by k_particleParams /
     // k_exceptionParams whenever a base value, an offset or a global parameter changes -- no re-sort, no tile rebuild, no graph re-capture,
@@ -370,7 +374,7 @@ public:
     DevBuf<T4> params14, paramsExcl; int n14 = 0, nExcl = 0;
     DevBuf<int> dSliceNeedAll, dSliceNeedSel; std::vector<int> sliceNeedSel;      // energy steps: every slice / the slices a derivative-only step (include_energy == 2) must produce
     DevBuf<double> dDispCoef, sliceE, sliceTotal;      // 64 partitioned copies of the raw [S][2] energies, and their sum (last kernel of an energy step)
-    bool energyPending = false, energySelective = false;      // the last energy step's sums are still on the device
+    bool energyPending = false;      // the last energy step's sums are still on the device
     std::vector<double> hostSliceE;   // raw energies of the last energy evaluation (device part + host terms)
     PmePlan<Real> pme, dpme; int nGrids = 0; std::vector<int> ownedSubsets; DevBuf<int> dStrayCount;      // [2] stray atoms of the own-atoms spreader (Coulomb mesh, dispersion mesh)
     bool needRebuild = true, paramsDirty = true; int stepsSinceRebuild = 0;
@@ -400,7 +404,29 @@ public:
     // of the positions staged when a rebuild starts (stageCtxPositions), so a list being built beside the steps does not depend on the order
     // the context has moved on to.
     struct CtxBinding { bool on = false; const void* posq = nullptr; const int* atomIndex = nullptr; int isDouble = 0, paddedN = 0; long long* force = nullptr; void* energy = nullptr; void* deriv = nullptr; int energyIsDouble = 0; } ctx;
-    DevBuf<int> dUserToCtx, dCtxScratch, dDerivSlot; DevBuf<unsigned char> ctxStage; DevBuf<double> dLambdas64; bool ctxAddTotal = false;
+    DevBuf<int> dUserToCtx, dCtxScratch, dDerivSlot; DevBuf<unsigned char> ctxStage; DevBuf<double> dLambdas64;
+    // What a step does with forces: Full -- a forces step (accumulate, deliver to the force output); None -- an energy-only step (the
+    // energy-only kernels: no force arithmetic, nothing cleared, nothing stored); Scratch -- the forces kernels into whatever set the views
+    // point at, no delivery (energy-only steps of sharded PME engines).
+    enum class StepForces { Full, None, Scratch };
+    enum class StepEnergy { None = 0, All = 1, Selected = 2 };      // (Selected: the slices of snb_set_energy_slices, a derivative-only step; the values are GraphKey::energy)
+    // What one step does.  Whoever asks for a step says all of it here: enqueueStep and what it calls read nothing else about the request,
+    // and the key of a captured step (graphKey) is computed from the same value.
+    struct StepRequest {
+        StepEnergy energy = StepEnergy::None;
+        bool direct = true, recip = true;
+        StepForces forces = StepForces::Full;
+        bool addCtxTotal = false;      // the bound context's total energy is added on the device
+        double* rowOut = nullptr;      // the row of a frame batch's table the step's finish kernel also writes
+        EvSet* ev = nullptr;      // a timed (eager) step's events
+    };
+    const int* sliceNeed(StepEnergy e) const { return e == StepEnergy::Selected ? dSliceNeedSel.p : dSliceNeedAll.p; }
+    GraphKey graphKey(const StepRequest& r) const {      // whatever changes what a captured step launches: the request, and the position, output and binding state
+        GraphKey k{devUserPos, posIsDouble, posStride4, r.direct, r.recip, (int)r.energy, outPtr, outIsDouble, outAccumulate};
+        if (ctx.on) { k.ctxPosq = ctx.posq; k.ctxForce = ctx.force; k.ctxEnergy = ctx.energy; k.ctxDeriv = ctx.deriv; k.ctxPadded = ctx.paddedN;
+                      k.ctxFlags = 1 | (ctx.isDouble ? 2 : 0) | (ctx.energyIsDouble ? 4 : 0) | (r.addCtxTotal ? 8 : 0); }
+        return k;
+    }
     void stageCtxPositions(void* dst) { launchCtxStagePositions(ctx.posq, ctx.isDouble, dUserToCtx.p, N, dst, stream); }
     void bindContext(const snb_context_binding* b) override {
         if (!b) {
@@ -924,14 +950,15 @@ public:
         const hipStream_t liveStream = stream; const void* livePos = devUserPos;
         const int liveCells[2] = {colCells[0], colCells[1]};
         swapListSets(); stream = streamBuild; devUserPos = src; sideBuilding = true;
-        bool ok = false;
-        try {
+        bool ok = false, built = false;
+        {
+            ScopeExit live([&] { sideBuilding = false; stream = liveStream; devUserPos = livePos; swapListSets(); if (!built) { colCells[0] = liveCells[0]; colCells[1] = liveCells[1]; } });
             ok = gpuRebuild();
             if (ok) { posRef.resize(Npad); HIPCHECK(hipMemcpyAsync(posRef.p, posq.p, sizeof(T4) * (size_t)Npad, hipMemcpyDeviceToDevice, stream)); }
             HIPCHECK(hipEventRecord(evBuilt, stream));
-        } catch (...) { sideBuilding = false; stream = liveStream; devUserPos = livePos; swapListSets(); colCells[0] = liveCells[0]; colCells[1] = liveCells[1]; throw; }
-        sideBuilding = false; stream = liveStream; devUserPos = livePos; swapListSets();
-        if (!ok) { colCells[0] = liveCells[0]; colCells[1] = liveCells[1]; HIPCHECK(hipEventSynchronize(evBuilt)); }      // (whatever was enqueued has finished with the scratch arrays)
+            built = ok;
+        }
+        if (!ok) HIPCHECK(hipEventSynchronize(evBuilt));      // (whatever was enqueued has finished with the scratch arrays)
         sidePending = ok;
         if (sw.verbose && ok) fprintf(stderr, "[snb] side build started after execute %lld\n", stepCounter - 1);
     }
@@ -1170,12 +1197,14 @@ public:
     }
 
     // ------------------------------------------------------------------------------------------
-    void fillPme(PmeParams<Real>& p, PmePlan<Real>& plan, bool wantEnergy) {
+    // need: the slices an energy step must produce (sliceNeed); cellsReady: this step's gather pass already wrote the Coulomb-mesh cells;
+    // trace: SNB_STEP_TRACE stamps of a replayed step
+    void fillPme(PmeParams<Real>& p, PmePlan<Real>& plan, bool wantEnergy, const int* need, bool cellsReady = false, bool trace = false) {
         p.d = plan.d; p.nsub = nGrids; p.natoms = Npad; p.posq = posq.p; p.sigeps = sigeps.p; p.atomSubset = atomSubset.p; p.atomGrid = atomGrid.p;
         p.cells = pmeCells.p;
         if (sw.pmeTrace) { if (!dPmeTrace.p) { dPmeTrace.resize(8); HIPCHECK(hipMemset(dPmeTrace.p, 0, 64)); } p.trace = dPmeTrace.p; }
-        p.stepTrace = (traceThisStep && plan.dispersion == (cfg.method == SNB_LJPME)) ? dStepTrace.p : nullptr;      // (the step's LAST mesh: its inverse z transform is what the second launch follows)
-        p.cellsReady = (!plan.dispersion && cellsFromGather) ? 1 : 0;
+        p.stepTrace = (trace && plan.dispersion == (cfg.method == SNB_LJPME)) ? dStepTrace.p : nullptr;      // (the step's LAST mesh: its inverse z transform is what the second launch follows)
+        p.cellsReady = (!plan.dispersion && cellsReady) ? 1 : 0;
         p.fixDev = dFixScale.p ? dFixScale.p + (plan.dispersion ? 2 : 0) : nullptr;      // (k_fixScale keeps it in step with the parameters)
         p.gridReal = plan.gridReal.p; p.gridCplx = plan.gridCplx.p; p.planeB = plan.gridCplxB.p; p.planeEterm = plan.planeEtermReady ? plan.planeEterm.p : nullptr; p.twx = plan.twx.p; p.twy = plan.twy.p; p.twz = plan.twz.p;
         p.modx = plan.modx.p; p.mody = plan.mody.p; p.modz = plan.modz.p;
@@ -1184,7 +1213,7 @@ public:
                              (box[3] * box[7] - box[4] * box[6]) * sc, -box[0] * box[7] * sc, box[0] * box[4] * sc};
         for (int i = 0; i < 9; i++) { p.recip[i] = (Real)r[i]; p.recipLo[i] = (Real)(r[i] - (double)p.recip[i]); }
         p.alpha = (Real)plan.alpha; p.volume = (Real)det; p.dispersion = plan.dispersion ? 1 : 0;
-        p.lambdas = dLambdas.p; p.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p; p.gridSubset = gridSubset.p; p.nsubTotal = nsub; p.mix = cfg.shard_count == 1 ? 1 : 0;
+        p.lambdas = dLambdas.p; p.sliceNeed = need; p.gridSubset = gridSubset.p; p.nsubTotal = nsub; p.mix = cfg.shard_count == 1 ? 1 : 0;
         p.mix16 = sw.mix16 ? 1 : 0;
         p.sliceE = sliceE.p; p.fpx = fpx.p; p.fpy = fpy.p; p.fpz = fpz.p; p.wantEnergy = wantEnergy ? 1 : 0;
         // brick kernels: the sort columns were cut for the Coulomb mesh; any mesh whose cells tile those columns can use them,
@@ -1225,7 +1254,7 @@ public:
         std::memcpy(plan.planeEtermKey, key, sizeof(key));
         plan.planeEtermReady = false;
         PmeParams<Real> pp; std::memset(&pp, 0, sizeof(pp));
-        fillPme(pp, plan, false);
+        fillPme(pp, plan, false, dSliceNeedAll.p);
         plan.planeEtermFilled = launchPlaneEterm<Real>(pp, plan.planeEterm.p, stream);
         plan.planeEtermReady = true;
     }
@@ -1282,17 +1311,22 @@ public:
     // What every evaluation starts with: the state checks, then the neighbour-list rules -- a due rebuild happens (in line, or as the exchange of a
     // list built beside the steps), a side build nothing can use any more is cancelled, changed parameter values are refreshed.  forces: a forces
     // step; anything else keeps the forces of the last forces step across a re-sort.  Returns whether the lists were rebuilt in line.
+    // The refusals about a periodic box x that every evaluation shares (prefix: what the caller puts before the messages about x): too small
+    // for the cutoff, not rectangular under classic Ewald.  The refusal of an Ewald engine without kmax is raised between the two
+    // (kmax: snb_execute's order), or alone (x == null: a batch raises it once, behind its frames).
+    void checkBox(const double* x, bool recip, const std::string& prefix, bool kmax) {
+        const double minAllowed = 1.999999 * cfg.cutoff;
+        if (x && !(x[0] >= minAllowed && x[4] >= minAllowed && x[8] >= minAllowed)) { err = prefix + "The periodic box size has decreased to less than twice the nonbonded cutoff."; throw (int)SNB_ERR_BOX_TOO_SMALL; }
+        if (cfg.method != SNB_Ewald || !recip) return;
+        if (kmax && (cfg.kmax[0] < 1 || cfg.kmax[1] < 1 || cfg.kmax[2] < 1)) { err = "Ewald: kmax must be given explicitly (snb_config.kmax)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (x && (x[3] != 0 || x[6] != 0 || x[7] != 0)) { err = prefix + "SlicedNonbondedForce: Ewald is not supported with non-rectangular boxes.  Use PME instead."; throw (int)SNB_ERR_UNSUPPORTED; }
+    }
     bool beginExecute(bool forces, int includeRecip) {
         if (!haveParticles) throw HipError{"snb_execute: particles were not set"};
         if (!havePositions) throw HipError{"snb_execute: positions were not set"};
         if (isPeriodic()) {
             if (!haveBox) throw HipError{"snb_execute: box was not set"};
-            const double minAllowed = 1.999999 * cfg.cutoff;
-            if (box[0] < minAllowed || box[4] < minAllowed || box[8] < minAllowed) { err = "The periodic box size has decreased to less than twice the nonbonded cutoff."; throw (int)SNB_ERR_BOX_TOO_SMALL; }
-        }
-        if (cfg.method == SNB_Ewald && includeRecip) {
-            if (cfg.kmax[0] < 1 || cfg.kmax[1] < 1 || cfg.kmax[2] < 1) { err = "Ewald: kmax must be given explicitly (snb_config.kmax)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
-            if (box[3] != 0 || box[6] != 0 || box[7] != 0) { err = "SlicedNonbondedForce: Ewald is not supported with non-rectangular boxes.  Use PME instead."; throw (int)SNB_ERR_UNSUPPORTED; }
+            checkBox(box, includeRecip != 0, "", true);
         }
         if (dLambdas.p == nullptr) setLambdas(lambdas.data());
         // rebuild_interval < 0: automatic -- rebuild when the displacement watch of the position-gather pass has seen an atom move
@@ -1342,8 +1376,10 @@ public:
         const bool rebuilding = beginExecute(forces, includeRecip);
         if (forces) outputWritten = outPtr != nullptr;      // (an energy-only step leaves the forces of the last forces step where they are)
         const bool energy = includeEnergy != 0;
-        energySelective = includeEnergy == 2;      // derivative-only step: only the slices named by snb_set_energy_slices
-        ctxAddTotal = ctx.on && ctx.energy && includeEnergy == 1 && !energyOut;      // (with energy != NULL the caller takes the total on the host)
+        StepRequest req;
+        req.energy = !energy ? StepEnergy::None : includeEnergy == 2 ? StepEnergy::Selected : StepEnergy::All;      // (2: derivative-only step)
+        req.direct = includeDirect != 0; req.recip = includeRecip != 0;
+        req.addCtxTotal = ctx.on && ctx.energy && includeEnergy == 1 && !energyOut;      // (with energy != NULL the caller takes the total on the host)
         if (forces) lastRecip = includeRecip && (isPme() || cfg.method == SNB_Ewald);
         // Forces-only steps replay a captured hipGraph (the ~14 small launches of a step are host-launch-bound otherwise:
         // 7-8 us of idle GPU between kernels).  Every 32nd step -- and every energy step -- is enqueued eagerly with HIP events
@@ -1360,81 +1396,82 @@ public:
             // updates a step graph (a rebuild it performs marks the graphs stale, as any rebuild does).  No force arithmetic, no force stores,
             // no force output -- except on sharded PME engines, whose energies come from the force interpolation: they run the forces kernels
             // into a scratch set.
-            EvSet* ev = nullptr;
             if (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0) {
-                ev = &ring[ringPos]; ringPos = (ringPos + 1) % RING;
-                if (ev->pending) harvest(*ev);
+                req.ev = &ring[ringPos]; ringPos = (ringPos + 1) % RING;
+                if (req.ev->pending) harvest(*req.ev);
             }
             const bool scratch = includeRecip && isPme() && nGrids > 0 && cfg.shard_count > 1;
+            req.forces = scratch ? StepForces::Scratch : StepForces::None;
             if (scratch) { forceScratch.resize((size_t)forceArrays() * Npad); pointForceViews(forceScratch.p); }
-            try { enqueueStep(energy, includeDirect != 0, includeRecip != 0, ev, scratch ? StepForces::Scratch : StepForces::None); }
-            catch (...) { if (scratch) pointForceViews(forceBuf.p); throw; }
-            if (scratch) pointForceViews(forceBuf.p);
-            if (ev) ev->pending = true;
-        } else {
-        haveForceStep = true;
-        GraphKey stepKey{devUserPos, posIsDouble, posStride4, includeDirect != 0, includeRecip != 0, energy ? (energySelective ? 2 : 1) : 0, outPtr, outIsDouble, outAccumulate};
-        if (ctx.on) { stepKey.ctxPosq = ctx.posq; stepKey.ctxForce = ctx.force; stepKey.ctxEnergy = ctx.energy; stepKey.ctxDeriv = ctx.deriv; stepKey.ctxPadded = ctx.paddedN;
-                      stepKey.ctxFlags = 1 | (ctx.isDouble ? 2 : 0) | (ctx.energyIsDouble ? 4 : 0) | (ctxAddTotal ? 8 : 0); }
-        bool haveGraph = false;
-        for (auto& g : graphs) if (g.key == stepKey && g.exec) haveGraph = true;
-        const bool eager = cfg.disable_graph || sw.noStepGraph || (rebuilding && (!haveGraph || sw.eagerRebuildStep)) || (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0);      // (no timed step while a list is being built beside it: the kernel timers are for kernels running alone)
-        if (eager) {
-            EvSet& ev = ring[ringPos]; ringPos = (ringPos + 1) % RING;
-            if (ev.pending) harvest(ev);
-            enqueueStep(energy, includeDirect != 0, includeRecip != 0, &ev);
-            ev.pending = true;
-        } else {
-            const GraphKey& key = stepKey;
-            hipGraphExec_t graphExec = nullptr;
-            CachedGraph* cached = nullptr;
-            for (auto& g : graphs) if (g.key == key) { cached = &g; if (!g.stale) graphExec = g.exec; break; }
-            if (!graphExec) {
-                if (!stream2 && (sw.concurrentPme || sw.overlap)) {   // created outside the capture
-                    int lo = 0, hi = 0;
-                    HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-                    HIPCHECK(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, sw.pmePrioLow ? lo : (sw.pmePrioHigh ? hi : (lo + hi) / 2)));
-                    HIPCHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evPairA, hipEventDisableTiming));
-                }
-                hipGraph_t graph = nullptr;
-                const auto tc0 = std::chrono::steady_clock::now();
-                HIPCHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-                try { enqueueStep(energy, includeDirect != 0, includeRecip != 0, nullptr); }
-                catch (...) { (void)hipStreamEndCapture(stream, &graph); if (graph) (void)hipGraphDestroy(graph); throw; }
-                HIPCHECK(hipStreamEndCapture(stream, &graph));
-                const auto tc1 = std::chrono::steady_clock::now();
-                bool updated = false;
-                if (cached && cached->exec && !sw.noGraphUpdate) {
-                    hipGraphNode_t errNode = nullptr; hipGraphExecUpdateResult res;
-                    if (hipGraphExecUpdate(cached->exec, graph, &errNode, &res) == hipSuccess) { graphExec = cached->exec; cached->stale = false; updated = true; }
-                    else (void)hipGetLastError();
-                }
-                if (!updated) {
-                    HIPCHECK(hipGraphInstantiate(&graphExec, graph, nullptr, nullptr, 0));
-                    if (cached) { if (cached->exec) (void)hipGraphExecDestroy(cached->exec); cached->exec = graphExec; cached->stale = false; }
-                    else if (graphs.size() < MAX_GRAPHS) graphs.push_back({key, graphExec, false});
-                    else { (void)hipGraphExecDestroy(graphs[graphVictim].exec); graphs[graphVictim] = {key, graphExec, false}; graphVictim = (graphVictim + 1) % MAX_GRAPHS; }
-                }
-                HIPCHECK(hipGraphDestroy(graph));
-                if (sw.verbose) fprintf(stderr, "[snb] step graph: capture %.0f us, %s %.0f us (host)\n", std::chrono::duration<double, std::micro>(tc1 - tc0).count(), updated ? "update" : "instantiate",
-                                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tc1).count());
+            {
+                ScopeExit views([&] { if (scratch) pointForceViews(forceBuf.p); });
+                enqueueStep(req);
             }
-            if (sw.verbose && rebuilding) {
-                const auto tl0 = std::chrono::steady_clock::now();
-                HIPCHECK(hipGraphLaunch(graphExec, stream));
-                const auto tl1 = std::chrono::steady_clock::now();
-                HIPCHECK(hipStreamSynchronize(stream));
-                fprintf(stderr, "[snb] rebuild step: graph launch %.0f us (host), step done after %.0f us\n", std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
-                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl0).count());
-            } else HIPCHECK(hipGraphLaunch(graphExec, stream));
-            if (sw.overlapDebug && sw.overlap && dOverlap.p && overlapDumps > 0) { overlapDumps--; dumpOverlapTable(); }
+            if (req.ev) req.ev->pending = true;
+        } else {
+            haveForceStep = true;
+            const GraphKey stepKey = graphKey(req);
+            bool haveGraph = false;
+            for (auto& g : graphs) if (g.key == stepKey && g.exec) haveGraph = true;
+            const bool eager = cfg.disable_graph || sw.noStepGraph || (rebuilding && (!haveGraph || sw.eagerRebuildStep)) || (timingInterval > 0 && !sidePending && execCount++ % timingInterval == 0);      // (no timed step while a list is being built beside it: the kernel timers are for kernels running alone)
+            if (eager) {
+                req.ev = &ring[ringPos]; ringPos = (ringPos + 1) % RING;
+                if (req.ev->pending) harvest(*req.ev);
+                enqueueStep(req);
+                req.ev->pending = true;
+            } else replayStep(stepKey, req, rebuilding);
         }
-        }      // forces step
         endExecute();
         if (energy) {
             energyPending = true;
             if (energyOut) { fetchSliceEnergies(); double e = 0; for (int i = 0; i < 2 * S; i++) e += lambdas[i] * hostSliceE[i]; *energyOut = e; }      // (synchronises)
         } else if (energyOut) *energyOut = 0.0;
+    }
+    // A replayed step: the captured graph of this key is found, or captured (and updated in place or instantiated anew, evicting the oldest
+    // of MAX_GRAPHS), then launched
+    void replayStep(const GraphKey& key, const StepRequest& req, bool rebuilding) {
+        hipGraphExec_t graphExec = nullptr;
+        CachedGraph* cached = nullptr;
+        for (auto& g : graphs) if (g.key == key) { cached = &g; if (!g.stale) graphExec = g.exec; break; }
+        if (!graphExec) {
+            if (!stream2 && (sw.concurrentPme || sw.overlap)) {   // created outside the capture
+                int lo = 0, hi = 0;
+                HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+                HIPCHECK(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, sw.pmePrioLow ? lo : (sw.pmePrioHigh ? hi : (lo + hi) / 2)));
+                HIPCHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&evPairA, hipEventDisableTiming));
+            }
+            hipGraph_t graph = nullptr;
+            const auto tc0 = std::chrono::steady_clock::now();
+            HIPCHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+            try { enqueueStep(req); }
+            catch (...) { (void)hipStreamEndCapture(stream, &graph); if (graph) (void)hipGraphDestroy(graph); throw; }
+            HIPCHECK(hipStreamEndCapture(stream, &graph));
+            const auto tc1 = std::chrono::steady_clock::now();
+            bool updated = false;
+            if (cached && cached->exec && !sw.noGraphUpdate) {
+                hipGraphNode_t errNode = nullptr; hipGraphExecUpdateResult res;
+                if (hipGraphExecUpdate(cached->exec, graph, &errNode, &res) == hipSuccess) { graphExec = cached->exec; cached->stale = false; updated = true; }
+                else (void)hipGetLastError();
+            }
+            if (!updated) {
+                HIPCHECK(hipGraphInstantiate(&graphExec, graph, nullptr, nullptr, 0));
+                if (cached) { if (cached->exec) (void)hipGraphExecDestroy(cached->exec); cached->exec = graphExec; cached->stale = false; }
+                else if (graphs.size() < MAX_GRAPHS) graphs.push_back({key, graphExec, false});
+                else { (void)hipGraphExecDestroy(graphs[graphVictim].exec); graphs[graphVictim] = {key, graphExec, false}; graphVictim = (graphVictim + 1) % MAX_GRAPHS; }
+            }
+            HIPCHECK(hipGraphDestroy(graph));
+            if (sw.verbose) fprintf(stderr, "[snb] step graph: capture %.0f us, %s %.0f us (host)\n", std::chrono::duration<double, std::micro>(tc1 - tc0).count(), updated ? "update" : "instantiate",
+                                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tc1).count());
+        }
+        if (sw.verbose && rebuilding) {
+            const auto tl0 = std::chrono::steady_clock::now();
+            HIPCHECK(hipGraphLaunch(graphExec, stream));
+            const auto tl1 = std::chrono::steady_clock::now();
+            HIPCHECK(hipStreamSynchronize(stream));
+            fprintf(stderr, "[snb] rebuild step: graph launch %.0f us (host), step done after %.0f us\n", std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
+                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl0).count());
+        } else HIPCHECK(hipGraphLaunch(graphExec, stream));
+        if (sw.overlapDebug && sw.overlap && dOverlap.p && overlapDumps > 0) { overlapDumps--; dumpOverlapTable(); }
     }
 
 
@@ -1471,15 +1508,14 @@ public:
         const bool frameBoxes = isPeriodic() && in.boxes != nullptr;
         if (isPeriodic()) {
             if (!frameBoxes && !haveBox) throw HipError{who + ": box was not set"};
-            const double minAllowed = 1.999999 * cfg.cutoff;
             for (int f = 0; f < (frameBoxes ? F : 1); f++) {
                 const double* x = frameBoxes ? in.boxes + 9 * (size_t)f : box;
-                if (x[1] != 0 || x[2] != 0 || x[5] != 0) throw HipError{who + ": frame " + std::to_string(f) + ": box vectors must be in reduced (lower triangular) form"};
-                if (!(x[0] >= minAllowed && x[4] >= minAllowed && x[8] >= minAllowed)) { err = who + ": frame " + std::to_string(f) + ": The periodic box size has decreased to less than twice the nonbonded cutoff."; throw (int)SNB_ERR_BOX_TOO_SMALL; }
-                if (cfg.method == SNB_Ewald && recip && (x[3] != 0 || x[6] != 0 || x[7] != 0)) { err = who + ": frame " + std::to_string(f) + ": SlicedNonbondedForce: Ewald is not supported with non-rectangular boxes.  Use PME instead."; throw (int)SNB_ERR_UNSUPPORTED; }
+                const std::string prefix = who + ": frame " + std::to_string(f) + ": ";
+                if (x[1] != 0 || x[2] != 0 || x[5] != 0) throw HipError{prefix + "box vectors must be in reduced (lower triangular) form"};
+                checkBox(x, recip, prefix, false);
             }
         }
-        if (cfg.method == SNB_Ewald && recip && (cfg.kmax[0] < 1 || cfg.kmax[1] < 1 || cfg.kmax[2] < 1)) { err = "Ewald: kmax must be given explicitly (snb_config.kmax)"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        checkBox(nullptr, recip, "", true);
     }
     // The frame loop of a batch, for any kind of step: step(f) enqueues, on `stream`, what is evaluated at frame f -- the lists in use are
     // that frame's, box and devUserPos are set -- and everything it enqueues precedes evFrameStep[f & 1]: the build of frame f + 2 overwrites
@@ -1495,13 +1531,13 @@ public:
         const long long discardedBefore = sideDiscarded; const int savedPredict = npadPredict;
         const bool hostFrames = in.hostFrames;
         const size_t frameBytes = (size_t)N * (in.stride4 ? 4 : 3) * (in.isDouble ? 8 : 4);
-        auto restore = [&]() {
+        ScopeExit restore([&] {
             devUserPos = savedPos; posIsDouble = savedIsDouble; posStride4 = savedStride4; havePositions = savedHavePos; haveBox = savedHaveBox;
             for (int i = 0; i < 9; i++) box[i] = savedBox[i];
-            frameRow = nullptr; plainSort = false; energySelective = false;
+            plainSort = false;
             if (savedPredict > 0) npadPredict = savedPredict;      // (MD rebuilds size their arrays as they did before the batch; an engine that had no prediction yet keeps the batch's, so that the next batch pipelines from its second frame)
             needRebuild = true;      // the lists in memory belong to the last frame
-        };
+        });
         try {
             if (dLambdas.p == nullptr) setLambdas(lambdas.data());
             if (sidePending) cancelSideBuild();      // (an MD side build in flight: its list would come into use after frames it knows nothing of)
@@ -1569,11 +1605,9 @@ public:
             fstats.n_batches++; fstats.n_frames += F; fstats.n_built_beside += nBeside; fstats.n_built_in_line += nInLine; fstats.n_side_discarded += sideDiscarded - discardedBefore; fstats.last_batch_ms = 0;
             if (finish()) fstats.last_batch_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         } catch (...) {
-            if (sidePending) { try { cancelSideBuild(); } catch (...) {} }
-            restore();
+            if (sidePending) { try { cancelSideBuild(); } catch (...) {} }      // (before the restore)
             throw;
         }
-        restore();
     }
     void evaluateFrames(const snb_frame_batch* b) override {
         const auto t0 = std::chrono::steady_clock::now();
@@ -1592,14 +1626,11 @@ public:
         const size_t rowLen = (size_t)S * 2;
         const bool hostOut = b->out_is_device == 0;
         double* rows = b->slice_energies;
-        if (hostOut) { frameRows.resize((size_t)F * rowLen); rows = frameRows.p; }
+        if (hostOut) { frameTab.resize((size_t)F * rowLen); rows = frameTab.p; }
+        StepRequest req;      // one energy-only step per frame, its finish kernel writing the frame's row as well
+        req.energy = b->mode == 2 ? StepEnergy::Selected : StepEnergy::All; req.direct = direct; req.recip = recip; req.forces = StepForces::None;
         runFrames(in, t0,
-            [&](int f) {      // one energy-only step, its finish kernel writing the frame's row as well
-                energySelective = b->mode == 2; ctxAddTotal = false;
-                frameRow = rows + (size_t)f * rowLen;
-                enqueueStep(true, direct, recip, nullptr, StepForces::None);
-                frameRow = nullptr;
-            },
+            [&](int f) { req.rowOut = rows + (size_t)f * rowLen; enqueueStep(req); },
             [&]() {
                 double* states = b->state_energies;
                 if (K > 0) {
@@ -1654,10 +1685,11 @@ public:
         energyPending = false;
     }
 
-    // the pair kernels' view of the lists in use and of the method (p zeroed by the caller); the launch-specific fields stay with the caller
-    void fillDirect(DirectParams<Real>& p) {
+    // the pair kernels' view of the lists in use and of the method (p zeroed by the caller; need: the slices an energy step must produce);
+    // the launch-specific fields stay with the caller
+    void fillDirect(DirectParams<Real>& p, const int* need) {
         p.posq = posq.p; p.sigeps = sigeps.p; p.blockSubset = blockSubset.p; p.workItems = workItems.p;
-        p.tileJ = tileJ.p; p.tileInfo = tileInfo.p; p.masks = masks.p; p.fx = fx.p; p.fy = fy.p; p.fz = fz.p; p.fs = fstride; p.fixed = fixedForces(); p.sliceE = sliceE.p; p.lambdas = dLambdas.p; p.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p;
+        p.tileJ = tileJ.p; p.tileInfo = tileInfo.p; p.masks = masks.p; p.fx = fx.p; p.fy = fy.p; p.fz = fz.p; p.fs = fstride; p.fixed = fixedForces(); p.sliceE = sliceE.p; p.lambdas = dLambdas.p; p.sliceNeed = need;
         const int r = cfg.shard_rank, c = cfg.shard_count;
         (void)r; (void)c;
         p.workStart = 0; p.workStride = 1; p.numWork = numWorkItems;      // the lists hold only the i-blocks this engine owns (block % shard_count == shard_rank)
@@ -1682,8 +1714,8 @@ public:
         p.boxDiag[0] = (Real)box[0]; p.boxDiag[1] = (Real)box[4]; p.boxDiag[2] = (Real)box[8];
     }
     // ... and of the O(N) pair lists: 1-4 exceptions and Ewald exclusion corrections
-    void fillPairLists(PairListParams<Real>& q) {
-        q.posq = posq.p; q.fx = fx.p; q.fy = fy.p; q.fz = fz.p; q.fs = fstride; q.fixed = fixedForces(); q.sliceE = sliceE.p; q.lambdas = dLambdas.p; q.sliceNeed = energySelective ? dSliceNeedSel.p : dSliceNeedAll.p;
+    void fillPairLists(PairListParams<Real>& q, const int* need) {
+        q.posq = posq.p; q.fx = fx.p; q.fy = fy.p; q.fz = fz.p; q.fs = fstride; q.fixed = fixedForces(); q.sliceE = sliceE.p; q.lambdas = dLambdas.p; q.sliceNeed = need;
         const bool exPeriodic = (cfg.method == SNB_NoCutoff || cfg.method == SNB_CutoffNonPeriodic) ? false : cfg.exceptions_periodic != 0;
         q.periodic = exPeriodic ? 1 : 0; q.imageOffset = imageOffset.p;
         q.sigeps = sigeps.p; q.blockSubset = blockSubset.p; q.exclStart = exclStart.p; q.exclList = exclList.p; q.nSlices = S; q.sortedToUser = dSortedToUser.p; q.userToSorted = dUserToSorted.p;
@@ -1693,12 +1725,41 @@ public:
         q.nExclAtoms = (cfg.method >= SNB_Ewald && nExcl > 0) ? Npad : 0;
     }
 
-    // What a step does with forces: Full -- a forces step (accumulate, deliver to the force output); None -- an energy-only step (the
-    // energy-only kernels: no force arithmetic, nothing cleared, nothing stored); Scratch -- the forces kernels into whatever set the views
-    // point at, no delivery (energy-only steps of sharded PME engines).
-    enum class StepForces { Full, None, Scratch };
-    void enqueueStep(bool energy, bool includeDirect, bool includeRecip, EvSet* ev, StepForces fmode = StepForces::Full) {
+    // The position-gather pass that opens a step or an atom pass: sorted positions, the displacement watch, `clearArrays` cleared force
+    // arrays, and what gc is filled with here -- (recip, PME on the brick path) the packed Coulomb-mesh cell of every atom and the zeroed
+    // stray counters, (clearEnergy) the cleared slice-energy partitions, (graphStep: a replayed forces step) the zeroed overlap counters
+    // and the trace.  Returns whether the pass writes the mesh cells.
+    bool enqueueGather(bool recip, bool clearEnergy, bool graphStep, int clearArrays) {
+        GatherCells<Real> gc;
+        std::memset(&gc, 0, sizeof(gc));
+        bool cells = false;
+        if (recip && isPme() && nGrids > 0) {
+            PmeParams<Real> pp;
+            std::memset(&pp, 0, sizeof(pp));
+            fillPme(pp, pme, false, dSliceNeedAll.p);
+            if (pp.sortNcx > 0 && pp.colRange != nullptr) {
+                for (int i = 0; i < 9; i++) { gc.recip[i] = pp.recip[i]; gc.recipLo[i] = pp.recipLo[i]; }
+                gc.nx = pp.d.nx; gc.ny = pp.d.ny; gc.nz = pp.d.nz; gc.cells = pp.cells; gc.atomGrid = pp.atomGrid;
+                cells = true;
+            }
+        }
+        if (cfg.neighbor_padding > 0 && posRef.p) {
+            gc.posRef = posRef.p; gc.flags = dDispFlags;
+            const double half = 0.5 * cfg.neighbor_padding;
+            gc.fail2 = (Real)(half * half); gc.warn2 = (Real)(0.64 * half * half);      // rebuild request at 80 % of skin/2: the flag is read one step late
+        }
+        if (clearEnergy) { gc.clearE = sliceE.p; gc.nClearE = S * 2 * SNB_SLICE_E_PARTS; }
+        if (recip && isPme() && dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
+        if (graphStep && sw.overlap && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
+        gc.stepTrace = graphStep ? dStepTrace.p : nullptr;      // (SNB_STEP_TRACE; replayed steps only: the stamps of the last one are printed when the engine is destroyed)
+        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, clearArrays, gc, stream); }
+        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, clearArrays, gc, stream);
+        return cells;
+    }
+    void enqueueStep(const StepRequest& r) {
         struct StampScope { StampScope(KernelStamps* k) { g_stamps = k; } ~StampScope() { g_stamps = nullptr; } };
+        const bool energy = r.energy != StepEnergy::None, includeDirect = r.direct, includeRecip = r.recip;
+        EvSet* const ev = r.ev; const StepForces fmode = r.forces; const int* const need = sliceNeed(r.energy);
         const bool forces = fmode != StepForces::None;
         const bool graphStep = !ev && fmode == StepForces::Full;      // (replayed forces steps: the only ones that overlap, fork or trace)
         const bool ctxForces = ctx.on && ctx.force && fmode == StepForces::Full;      // bound context: the step's last kernel adds into its fixed-point buffer
@@ -1706,8 +1767,8 @@ public:
         EnergyOut eo;
         std::memset(&eo, 0, sizeof(eo));
         if (ctx.on && energy) {
-            eo.lambdas = dLambdas64.p; eo.energy = ctxAddTotal ? ctx.energy : nullptr; eo.deriv = ctx.deriv; eo.derivSlot = dDerivSlot.p;
-            eo.need = energySelective ? dSliceNeedSel.p : nullptr; eo.isDouble = ctx.energyIsDouble;
+            eo.lambdas = dLambdas64.p; eo.energy = r.addCtxTotal ? ctx.energy : nullptr; eo.deriv = ctx.deriv; eo.derivSlot = dDerivSlot.p;
+            eo.need = r.energy == StepEnergy::Selected ? need : nullptr; eo.isDouble = ctx.energyIsDouble;
         }
         if (ev) for (int k = 0; k < 16; k++) ev->ks.used[k] = false;
         const bool noStamps = sw.noKernelStamps;
@@ -1717,32 +1778,8 @@ public:
         const bool fullStamps = ev && !noStamps && (stampCounter++ % 3 == 0);
         StampScope stampScope(fullStamps ? &ev->ks : nullptr);
         if (ev) HIPCHECK(hipEventRecord(ev->e[0], stream));
-        // one pass: sorted positions, cleared force arrays, and (PME on the brick path) the packed Coulomb-mesh cell of every atom
-        GatherCells<Real> gc;
-        std::memset(&gc, 0, sizeof(gc));
-        cellsFromGather = false;
-        if (includeRecip && isPme() && nGrids > 0) {
-            PmeParams<Real> pp;
-            std::memset(&pp, 0, sizeof(pp));
-            fillPme(pp, pme, false);
-            if (pp.sortNcx > 0 && pp.colRange != nullptr) {
-                for (int i = 0; i < 9; i++) { gc.recip[i] = pp.recip[i]; gc.recipLo[i] = pp.recipLo[i]; }
-                gc.nx = pp.d.nx; gc.ny = pp.d.ny; gc.nz = pp.d.nz; gc.cells = pp.cells; gc.atomGrid = pp.atomGrid;
-                cellsFromGather = true;
-            }
-        }
-        if (cfg.neighbor_padding > 0 && posRef.p) {
-            gc.posRef = posRef.p; gc.flags = dDispFlags;
-            const double half = 0.5 * cfg.neighbor_padding;
-            gc.fail2 = (Real)(half * half); gc.warn2 = (Real)(0.64 * half * half);      // rebuild request at 80 % of skin/2: the flag is read one step late
-        }
-        if (energy && Npad > 0) { gc.clearE = sliceE.p; gc.nClearE = S * 2 * SNB_SLICE_E_PARTS; }
-        if (includeRecip && isPme() && dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
-        if (graphStep && sw.overlap && dOverlap.p) { gc.zeroInts2 = dOverlap.p; gc.nZeroInts2 = SNB_OVERLAP_INTS; }
-        traceThisStep = graphStep && dStepTrace.p != nullptr;      // (SNB_STEP_TRACE; replayed steps only: the stamps of the last one are printed when the engine is destroyed)
-        gc.stepTrace = traceThisStep ? dStepTrace.p : nullptr;
-        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream); }
-        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, forces ? forceArrays() : 0, gc, stream);
+        const bool trace = graphStep && dStepTrace.p != nullptr;
+        const bool cellsReady = enqueueGather(includeRecip, energy && Npad > 0, graphStep, forces ? forceArrays() : 0);
         if (energy && Npad <= 0) launchZeroFill(sliceE.p, sizeof(double) * S * 2 * SNB_SLICE_E_PARTS, stream);      // (inside the step graph: a kernel, not a memset node)
         // Opt-in (SNB_CONCURRENT_PME=1): forces-only graph steps run the reciprocal pipeline on a second stream beside the pair
         // kernel (disjoint force arrays fx.. / fpx..).  Timed (eager) steps stay serial so the per-kernel event timers stay clean.
@@ -1759,17 +1796,17 @@ public:
         std::memset(&q, 0, sizeof(q));
         // O(N) pair lists: one rank only when sharded -- the LAST one, which carries no PME grid once there are more ranks than grids
         const bool haveLists = includeDirect && cfg.shard_rank == cfg.shard_count - 1;
-        if (haveLists) fillPairLists(q);
+        if (haveLists) fillPairLists(q, need);
         bool listsDone = !haveLists, kernelTimed = false, finished = false, energyFinished = false;
         DirectParams<Real> directB; int directMc = 0;      // overlapped step: the second launch of the tile kernel
         std::memset(&directB, 0, sizeof(directB));
         if (includeDirect) {
             DirectParams<Real> p;
             std::memset(&p, 0, sizeof(p));
-            fillDirect(p);
+            fillDirect(p, need);
             const int mc = methodClass();
             const bool noFuse = sw.noFusedLists;
-            p.stepTrace = traceThisStep ? dStepTrace.p : nullptr; p.traceSlot = 2;
+            p.stepTrace = trace ? dStepTrace.p : nullptr; p.traceSlot = 2;
             if (overlap) {      // first launch: resident beside the reciprocal pipeline, at most sw.overlapCuLimit work-groups per CU
                 p.workCounter = dOverlap.p; p.cuSlots = dOverlap.p + SNB_WORK_SHARDS * 32; p.cuLimit = sw.overlapCuLimit;
                 p.cuBaseMax = sw.overlapByCount ? -1 : 0x7fffffff;
@@ -1813,12 +1850,12 @@ public:
                     HIPCHECK(hipStreamWaitEvent(stream2, evPairA, 0));
                 };
                 // (energy-only steps: each mesh ends with its slice-energy Gram sums -- no mix, no inverse transforms, no interpolation)
-                fillPme(pp, pme, energy); withOutput(pp, cfg.method != SNB_LJPME); pp.energyOnly = forces ? 0 : 1;
+                fillPme(pp, pme, energy, need, cellsReady, trace); withOutput(pp, cfg.method != SNB_LJPME); pp.energyOnly = forces ? 0 : 1;
                 runPmeFront(pp, pmeStream);
                 if (cfg.method != SNB_LJPME) beforeLastInterpolation();
                 if (forces) { finished = launchPmeInterpolate<Real>(pp, pmeStream); energyFinished = finished && pp.finOut != nullptr; }
                 if (cfg.method == SNB_LJPME) {
-                    fillPme(pp, dpme, energy); withOutput(pp, true); pp.energyOnly = forces ? 0 : 1;
+                    fillPme(pp, dpme, energy, need, cellsReady, trace); withOutput(pp, true); pp.energyOnly = forces ? 0 : 1;
                     runPmeFront(pp, pmeStream);
                     beforeLastInterpolation();
                     if (forces) { finished = launchPmeInterpolate<Real>(pp, pmeStream); energyFinished = finished && pp.finOut != nullptr; }
@@ -1835,7 +1872,7 @@ public:
         if (energy) {
             const SliceFinish f = makeSliceFinish(includeDirect, includeRecip);
             if (!(finished && energyFinished))
-            launchFinishSliceEnergies(sliceE.p, sliceTotal.p, 2 * S, f, eo, stream, frameRow);
+            launchFinishSliceEnergies(sliceE.p, sliceTotal.p, 2 * S, f, eo, stream, r.rowOut);
         }
         if (ev) HIPCHECK(hipEventRecord(ev->e[4], stream));
     }
@@ -1870,33 +1907,15 @@ public:
     // step of a group batch's frame.  forces chooses the kernels only: the pair and stencil launchers of atomforce.hip, else of atomenergy.hip.
     void enqueueAtomPass(bool includeDirect, bool includeRecip, double* tab, int rowDoubles, bool forces) {
         launchZeroFill(tab, sizeof(double) * (size_t)Npad * nsub * rowDoubles, stream);
+        // what the pass asks of the shared step code is fixed: every slice, no trace, no row of a batch -- nothing of an earlier snb_execute
+        const int* const need = sliceNeed(StepEnergy::All);
         // the position-gather pass of a step that clears nothing: sorted positions, the Coulomb-mesh cells, the displacement watch
         const bool recip = includeRecip && isPme() && nGrids > 0;
-        GatherCells<Real> gc;
-        std::memset(&gc, 0, sizeof(gc));
-        cellsFromGather = false; traceThisStep = false;
-        if (recip) {
-            PmeParams<Real> pp;
-            std::memset(&pp, 0, sizeof(pp));
-            fillPme(pp, pme, false);
-            if (pp.sortNcx > 0 && pp.colRange != nullptr) {
-                for (int i = 0; i < 9; i++) { gc.recip[i] = pp.recip[i]; gc.recipLo[i] = pp.recipLo[i]; }
-                gc.nx = pp.d.nx; gc.ny = pp.d.ny; gc.nz = pp.d.nz; gc.cells = pp.cells; gc.atomGrid = pp.atomGrid;
-                cellsFromGather = true;
-            }
-            if (dStrayCount.p) { gc.zeroInts = dStrayCount.p; gc.nZeroInts = 2; }
-        }
-        if (cfg.neighbor_padding > 0 && posRef.p) {
-            gc.posRef = posRef.p; gc.flags = dDispFlags;
-            const double half = 0.5 * cfg.neighbor_padding;
-            gc.fail2 = (Real)(half * half); gc.warn2 = (Real)(0.64 * half * half);
-        }
-        if (ctx.on) { gc.userToCtx = dUserToCtx.p; launchGatherPositions<Real>(ctx.posq, ctx.isDouble, 1, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream); }
-        else launchGatherPositions<Real>(devUserPos, posIsDouble, posStride4, dSortedToUser.p, imageOffset.p, posq.p, Npad, forceBase, 0, gc, stream);
+        const bool cellsReady = enqueueGather(recip, false, false, 0);
         if (includeDirect) {
             DirectParams<Real> p; PairListParams<Real> q;
             std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
-            fillDirect(p); fillPairLists(q);
+            fillDirect(p, need); fillPairLists(q, need);
             if (forces) launchAtomForcePairs<Real>(p, methodClass(), wrapMode, &q, tab, stream);
             else launchAtomPairs<Real>(p, methodClass(), wrapMode, &q, tab, stream);
         }
@@ -1904,7 +1923,7 @@ public:
             PmeParams<Real> pp;
             std::memset(&pp, 0, sizeof(pp));
             auto mesh = [&](PmePlan<Real>& m) {      // the unmixed front of one mesh, then its part of every atom's row
-                fillPme(pp, m, false); pp.mix = 0;
+                fillPme(pp, m, false, need, cellsReady); pp.mix = 0;
                 runPmeFront(pp, stream);
                 if (forces) launchAtomField<Real>(pp, tab, stream);
                 else launchAtomPotential<Real>(pp, tab, stream);
@@ -1928,18 +1947,25 @@ public:
             if (cfg.method == SNB_Ewald && includeRecip) { err = who + ": the reciprocal sum of classic Ewald is not attributed to atoms (use PME, or include_reciprocal = 0)"; throw (int)SNB_ERR_UNSUPPORTED; }
         }
     }
-    void evaluateAtomEnergies(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
-        refuseAtomCall("snb_evaluate_atom_energies", "atom_energies", out, includeDirect != 0, includeRecip != 0, true, true);
+    // snb_evaluate_atom_energies, or (forces) snb_evaluate_atom_forces: the kind of table sets the row (2 or 6 doubles), the working and
+    // staging buffers (each call's own) and the finish kernel
+    static constexpr int atomRow(bool forces) { return forces ? 6 : 2; }
+    DevBuf<double>& atomTable(bool forces) { return forces ? atomFTab : atomTab; }
+    void evaluateAtomTable(bool forces, int includeDirect, int includeRecip, double* out, int outIsDevice) override {
+        const bool direct = includeDirect != 0, recip = includeRecip != 0;
+        refuseAtomCall(forces ? "snb_evaluate_atom_forces" : "snb_evaluate_atom_energies", forces ? "atom_forces" : "atom_energies", out, direct, recip, true, true);
         beginExecute(false, includeRecip);
-        const size_t tabN = (size_t)Npad * nsub * 2, outN = (size_t)N * nsub * 2;
-        atomTab.resize(tabN);
-        if (!outIsDevice) atomOut.resize(outN);
-        double* const dst = outIsDevice ? out : atomOut.p;
-        enqueueAtomPass(includeDirect != 0, includeRecip != 0, atomTab.p, 2, false);
-        launchAtomFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, N, nsub, makeAtomFinish(includeDirect != 0, includeRecip != 0), dst, stream);
+        DevBuf<double>& tab = atomTable(forces); DevBuf<double>& staged = forces ? atomFOut : atomOut;
+        const size_t tabN = (size_t)Npad * nsub * atomRow(forces), outN = (size_t)N * nsub * atomRow(forces);
+        tab.resize(tabN);
+        if (!outIsDevice) staged.resize(outN);
+        double* const dst = outIsDevice ? out : staged.p;
+        enqueueAtomPass(direct, recip, tab.p, atomRow(forces), forces);
+        if (forces) launchAtomForceFinish(tab.p, dUserToSorted.p, N, nsub, dst, stream);
+        else launchAtomFinish<Real>(tab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, N, nsub, makeAtomFinish(direct, recip), dst, stream);
         endExecute();
         if (!outIsDevice) {
-            HIPCHECK(hipMemcpyAsync(out, atomOut.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipMemcpyAsync(out, staged.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
             HIPCHECK(hipStreamSynchronize(stream));
         }
     }
@@ -1947,8 +1973,8 @@ public:
     // ------------------------------------------------------------------------------------------
     // Per-group interaction energies over stored frames (snb_evaluate_group_energies): the table above summed over
     // lists of atoms, on the device, per frame.  With frames: the frame loop of snb_evaluate_frames (runFrames) with the atom pass and the
-    // group finish as the step.  Without: one evaluation under the rules of evaluateAtomEnergies.  Writes only its output: the working table,
-    // the chunk sums and the staging of a host result are its own (atomTab is shared with evaluateAtomEnergies, which refills it).
+    // group finish as the step.  Without: one evaluation under the rules of snb_evaluate_atom_energies.  Writes only its output: the working table,
+    // the chunk sums and the staging of a host result are its own (atomTab is shared with snb_evaluate_atom_energies, which refills it).
     // ------------------------------------------------------------------------------------------
     DevBuf<int> dGroupPlan; DevBuf<double> groupPartial, groupOut;
     // What snb_evaluate_group_energies and snb_evaluate_group_forces check, in the order it is raised -- everything before anything is
@@ -1973,137 +1999,100 @@ public:
         if (in.positions) checkFrames(in, recip);
         return true;
     }
-    void evaluateGroupEnergies(const snb_group_batch* b) override {
+    // The two group calls: the checks; the lists packed with the work lists of the two mappings, one upload per call through the pinned ring;
+    // then the engine's current state as the atom calls take it, or the frame loop with the atom pass and the group finish as the step; a host
+    // result is copied back behind one synchronisation.  The table is the kind's own (atomTable).  Each call brings what is its own: sizes(plan)
+    // sizes its chunk sums and staging (and uploads its states), finish(plan, f) launches its finish kernel for frame f -- before
+    // evFrameStep[f & 1]: it reads the frame's list set -- and copyBack() enqueues the copies of a host result.
+    struct GroupInput { int G; const int32_t* start; const int32_t* atoms; bool direct, recip, hostOut; };
+    template <typename Sizes, typename Finish, typename CopyBack>
+    void evaluateGroups(bool forces, const FrameInput& in, const GroupInput& g, bool outputs, const char* outputNames, Sizes&& sizes, Finish&& finish, CopyBack&& copyBack) {
         const auto t0 = std::chrono::steady_clock::now();
-        const int G = b->n_groups, F = b->n_frames;
-        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
-        const FrameInput in{"snb_evaluate_group_energies", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
-        if (!checkGroupCall(in, b->group_energies != nullptr, "group_energies", G, b->group_start, b->group_atoms, direct, recip)) return;
-        // ---- the lists, packed with the work lists of the two mappings: one upload per call, through the pinned ring
+        if (!checkGroupCall(in, outputs, outputNames, g.G, g.start, g.atoms, g.direct, g.recip)) return;
         GroupPlan plan;
-        planGroups(G, b->group_start, plan);
-        std::copy(b->group_atoms, b->group_atoms + b->group_start[G], plan.packed.begin() + plan.offAtoms);
-        const size_t rowLen = (size_t)G * nsub * 2;
-        const bool hostOut = b->out_is_device == 0;
-        double* rows = b->group_energies;
-        auto prepare = [&]() {
-            pinned.upload(dGroupPlan, plan.packed, stream);
-            groupPartial.resize((size_t)std::max(plan.nChunks, 1) * nsub * 2);
-            if (hostOut) { groupOut.resize((size_t)F * rowLen); rows = groupOut.p; }
-        };
-        auto groupFinish = [&](int f) {
-            launchGroupFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, nsub, makeAtomFinish(direct, recip), plan, dGroupPlan.p, groupPartial.p, rows + (size_t)f * rowLen, stream);
+        planGroups(g.G, g.start, plan);
+        std::copy(g.atoms, g.atoms + g.start[g.G], plan.packed.begin() + plan.offAtoms);
+        DevBuf<double>& tab = atomTable(forces);
+        auto prepare = [&]() { pinned.upload(dGroupPlan, plan.packed, stream); sizes(plan); };
+        auto pass = [&](int f, int npad) {
+            tab.resize((size_t)npad * nsub * atomRow(forces));
+            enqueueAtomPass(g.direct, g.recip, tab.p, atomRow(forces), forces);
+            finish(plan, f);
         };
         auto deliver = [&]() {
-            if (!hostOut) return false;
-            HIPCHECK(hipMemcpyAsync(b->group_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+            if (!g.hostOut) return false;
+            copyBack();
             HIPCHECK(hipStreamSynchronize(stream));
             return true;
         };
-        if (!b->positions) {      // the engine's current state, as snb_evaluate_atom_energies takes it
-            beginExecute(false, recip);
+        if (!in.positions) {      // the engine's current state, as the atom calls take it
+            beginExecute(false, g.recip);
             prepare();
-            atomTab.resize((size_t)Npad * nsub * 2);
-            enqueueAtomPass(direct, recip, atomTab.p, 2, false);
-            groupFinish(0);
+            pass(0, Npad);
             endExecute();
             deliver();
             return;
         }
         prepare();
-        runFrames(in, t0,
-            [&](int f) {
-                // (sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
-                atomTab.resize((size_t)std::max(Npad, npadPredict) * nsub * 2);
-                enqueueAtomPass(direct, recip, atomTab.p, 2, false);
-                groupFinish(f);      // before evFrameStep[f & 1]: it reads userToSorted, blockSubset, posq and sigeps of this frame's list set
+        // (the table is sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
+        runFrames(in, t0, [&](int f) { pass(f, std::max(Npad, npadPredict)); }, deliver);
+    }
+    void evaluateGroupEnergies(const snb_group_batch* b) override {
+        const int G = b->n_groups, F = b->n_frames;
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0, hostOut = b->out_is_device == 0;
+        const FrameInput in{"snb_evaluate_group_energies", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
+        const size_t rowLen = (size_t)G * nsub * 2;
+        double* rows = b->group_energies;
+        evaluateGroups(false, in, {G, b->group_start, b->group_atoms, direct, recip, hostOut}, b->group_energies != nullptr, "group_energies",
+            [&](const GroupPlan& plan) {
+                groupPartial.resize((size_t)std::max(plan.nChunks, 1) * nsub * 2);
+                if (hostOut) { groupOut.resize((size_t)F * rowLen); rows = groupOut.p; }
             },
-            deliver);
+            [&](const GroupPlan& plan, int f) {      // (reads userToSorted, blockSubset, posq and sigeps of this frame's list set)
+                launchGroupFinish<Real>(atomTab.p, dUserToSorted.p, blockSubset.p, posq.p, sigeps.p, nsub, makeAtomFinish(direct, recip), plan, dGroupPlan.p, groupPartial.p, rows + (size_t)f * rowLen, stream);
+            },
+            [&]() { HIPCHECK(hipMemcpyAsync(b->group_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream)); });
     }
 
     // ------------------------------------------------------------------------------------------
     // Per-atom forces by partner subset and term (snb_evaluate_atom_forces): G[i][J][t] = -dE_raw[slice(s_i, J)][t]/dr_i.
-    // The frame, the refusals and the pass of evaluateAtomEnergies above, with the kernels of atomforce.hip: pair forces with every lambda 1
+    // The frame, the refusals and the pass of snb_evaluate_atom_energies above (evaluateAtomTable), with the kernels of atomforce.hip: pair forces with every lambda 1
     // into both ends' columns, the derivative part of the interpolation per (atom, held mesh) of the unmixed pipeline, no closed-form term
     // (none carries a force).  Writes only its table; working and staging tables are its own.
     // ------------------------------------------------------------------------------------------
     DevBuf<double> atomFTab, atomFOut;      // sorted-order working table [Npad][nsub][2][3]; user-order staging of a host result (both allocated at the first call)
-    void evaluateAtomForces(int includeDirect, int includeRecip, double* out, int outIsDevice) override {
-        refuseAtomCall("snb_evaluate_atom_forces", "atom_forces", out, includeDirect != 0, includeRecip != 0, true, true);
-        beginExecute(false, includeRecip);
-        const size_t tabN = (size_t)Npad * nsub * 6, outN = (size_t)N * nsub * 6;
-        atomFTab.resize(tabN);
-        if (!outIsDevice) atomFOut.resize(outN);
-        double* const dst = outIsDevice ? out : atomFOut.p;
-        enqueueAtomPass(includeDirect != 0, includeRecip != 0, atomFTab.p, 6, true);
-        launchAtomForceFinish(atomFTab.p, dUserToSorted.p, N, nsub, dst, stream);
-        endExecute();
-        if (!outIsDevice) {
-            HIPCHECK(hipMemcpyAsync(out, atomFOut.p, sizeof(double) * outN, hipMemcpyDeviceToHost, stream));
-            HIPCHECK(hipStreamSynchronize(stream));
-        }
-    }
 
     // ------------------------------------------------------------------------------------------
     // Per-group forces over stored frames, by subset and at lambda states (snb_evaluate_group_forces): the force
     // table summed over lists of atoms on the device, per frame, and contracted per atom with K lambda states.  evaluateGroupEnergies with
     // the force pass as the step and the group-force finish of atomforce.hip.  Writes only its outputs: the chunk sums, the device copy of
-    // the states and the staging of a host result are its own (atomFTab is shared with evaluateAtomForces, which refills it; the plan's
+    // the states and the staging of a host result are its own (atomFTab is shared with snb_evaluate_atom_forces, which refills it; the plan's
     // buffer with evaluateGroupEnergies, which uploads its own).
     // ------------------------------------------------------------------------------------------
     DevBuf<double> groupFPartial, groupFOut, groupFStates, dGroupLambdas;
     void evaluateGroupForces(const snb_group_force_batch* b) override {
-        const auto t0 = std::chrono::steady_clock::now();
         const int G = b->n_groups, F = b->n_frames, K = b->n_states;
-        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
         const FrameInput in{"snb_evaluate_group_forces", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
         if (K < 0) { err = std::string(in.who) + ": negative state count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
         const bool outputs = K > 0 ? (b->state_lambdas && b->state_forces) : b->group_forces != nullptr;
-        if (!checkGroupCall(in, outputs, K > 0 ? "state_lambdas and state_forces" : "group_forces", G, b->group_start, b->group_atoms, direct, recip)) return;
-        // ---- the lists, packed with the work lists of the two mappings, and the states: one upload each per call, through the pinned ring
-        GroupPlan plan;
-        planGroups(G, b->group_start, plan);
-        std::copy(b->group_atoms, b->group_atoms + b->group_start[G], plan.packed.begin() + plan.offAtoms);
         const bool wantRows = b->group_forces != nullptr, hostOut = b->out_is_device == 0;
         const size_t rowLen = (size_t)G * nsub * 6, stateLen = (size_t)K * G * 3;
         double* rows = b->group_forces; double* states = b->state_forces;
-        auto prepare = [&]() {
-            pinned.upload(dGroupPlan, plan.packed, stream);
-            if (K > 0) pinned.upload(dGroupLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * S * 2), stream);
-            groupFPartial.resize((size_t)std::max(plan.nChunks, 1) * ((wantRows ? (size_t)nsub * 6 : 0) + (size_t)K * 3));
-            if (hostOut && wantRows) { groupFOut.resize((size_t)F * rowLen); rows = groupFOut.p; }
-            if (hostOut && K > 0) { groupFStates.resize((size_t)F * stateLen); states = groupFStates.p; }
-        };
-        auto groupFinish = [&](int f) {
-            launchGroupForceFinish(atomFTab.p, dUserToSorted.p, blockSubset.p, nsub, plan, dGroupPlan.p, dGroupLambdas.p, K, groupFPartial.p, wantRows ? rows + (size_t)f * rowLen : nullptr,
-                                   K > 0 ? states + (size_t)f * stateLen : nullptr, stream);
-        };
-        auto deliver = [&]() {
-            if (!hostOut) return false;
-            if (wantRows) HIPCHECK(hipMemcpyAsync(b->group_forces, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
-            if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_forces, states, sizeof(double) * (size_t)F * stateLen, hipMemcpyDeviceToHost, stream));
-            HIPCHECK(hipStreamSynchronize(stream));
-            return true;
-        };
-        if (!b->positions) {      // the engine's current state, as snb_evaluate_atom_forces takes it
-            beginExecute(false, recip);
-            prepare();
-            atomFTab.resize((size_t)Npad * nsub * 6);
-            enqueueAtomPass(direct, recip, atomFTab.p, 6, true);
-            groupFinish(0);
-            endExecute();
-            deliver();
-            return;
-        }
-        prepare();
-        runFrames(in, t0,
-            [&](int f) {
-                // (sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
-                atomFTab.resize((size_t)std::max(Npad, npadPredict) * nsub * 6);
-                enqueueAtomPass(direct, recip, atomFTab.p, 6, true);
-                groupFinish(f);      // before evFrameStep[f & 1]: it reads userToSorted and blockSubset of this frame's list set
+        evaluateGroups(true, in, {G, b->group_start, b->group_atoms, b->include_direct != 0, b->include_reciprocal != 0, hostOut}, outputs, K > 0 ? "state_lambdas and state_forces" : "group_forces",
+            [&](const GroupPlan& plan) {      // the states: one upload per call, through the pinned ring
+                if (K > 0) pinned.upload(dGroupLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * S * 2), stream);
+                groupFPartial.resize((size_t)std::max(plan.nChunks, 1) * ((wantRows ? (size_t)nsub * 6 : 0) + (size_t)K * 3));
+                if (hostOut && wantRows) { groupFOut.resize((size_t)F * rowLen); rows = groupFOut.p; }
+                if (hostOut && K > 0) { groupFStates.resize((size_t)F * stateLen); states = groupFStates.p; }
             },
-            deliver);
+            [&](const GroupPlan& plan, int f) {      // (reads userToSorted and blockSubset of this frame's list set)
+                launchGroupForceFinish(atomFTab.p, dUserToSorted.p, blockSubset.p, nsub, plan, dGroupPlan.p, dGroupLambdas.p, K, groupFPartial.p, wantRows ? rows + (size_t)f * rowLen : nullptr,
+                                       K > 0 ? states + (size_t)f * stateLen : nullptr, stream);
+            },
+            [&]() {
+                if (wantRows) HIPCHECK(hipMemcpyAsync(b->group_forces, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+                if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_forces, states, sizeof(double) * (size_t)F * stateLen, hipMemcpyDeviceToHost, stream));
+            });
     }
 
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
@@ -2344,10 +2333,10 @@ snb_status snb_evaluate_frames(snb_handle h, const snb_frame_batch* b) {
     return guard(h, [&] { h->impl->evaluateFrames(b); });
 }
 snb_status snb_evaluate_atom_energies(snb_handle h, int32_t includeDirect, int32_t includeRecip, double* atomEnergies, int32_t outIsDevice) {
-    return guard(h, [&] { h->impl->evaluateAtomEnergies(includeDirect, includeRecip, atomEnergies, outIsDevice); });
+    return guard(h, [&] { h->impl->evaluateAtomTable(false, includeDirect, includeRecip, atomEnergies, outIsDevice); });
 }
 snb_status snb_evaluate_atom_forces(snb_handle h, int32_t includeDirect, int32_t includeRecip, double* atomForces, int32_t outIsDevice) {
-    return guard(h, [&] { h->impl->evaluateAtomForces(includeDirect, includeRecip, atomForces, outIsDevice); });
+    return guard(h, [&] { h->impl->evaluateAtomTable(true, includeDirect, includeRecip, atomForces, outIsDevice); });
 }
 snb_status snb_evaluate_group_energies(snb_handle h, const snb_group_batch* b) {
     if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_energies: null batch"; return SNB_ERR_INVALID_ARGUMENT; }

@@ -339,6 +339,29 @@ def test_device_output_equals_host_output(t24, snb):
     eng.close()
 
 
+def test_table_ignores_the_selection_of_an_earlier_step(t24, snb):
+    """The table takes every slice whatever the last snb_execute selected: a derivative-only forces step with slice 0 alone selected
+    (snb_set_energy_slices, include_energy == 2) between two tables of one state changes neither the table (the bound of two tables of one
+    state, above) nor, bit for bit, what snb_get_forces returned right after the step."""
+    import torch
+    w = t24.w; n = len(w["q"])
+    eng = bench.Engine(snb, w, 4, 54, 0, "mixed", 0, 0, 1, 0.1, 1 << 30)
+    pos = _dev(w["pos"], False)
+    eng.set_positions_device(pos.data_ptr(), False)
+    before = _table(eng, n, 4)
+    eng.set_energy_slices([1] + [0] * (S4 - 1))
+    eng.ok(eng.L.snb_execute(eng.h, 1, 2, 1, 1, None))
+    f_step = torch.zeros((n, 3), dtype=torch.float32, device="cuda"); eng.forces_to(f_step.data_ptr(), False); eng.sync()
+    after = _table(eng, n, 4)
+    assert np.isfinite(after).all() and np.abs(after).max() > 1.0
+    err = aet.rel(after, before)
+    print("table after a selective step against the table before: %.3e" % err)
+    assert err < 1e-9
+    f_after = torch.zeros_like(f_step); eng.forces_to(f_after.data_ptr(), False); eng.sync()
+    assert torch.equal(f_step, f_after)
+    eng.close()
+
+
 # ---- 10. status codes ------------------------------------------------------------------------------------------------------------------
 def test_status_codes(t24, snb, oracle):
     capi = snb.capi; L = capi.lib()
