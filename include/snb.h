@@ -431,6 +431,54 @@ typedef struct {
 } snb_group_force_batch;
 snb_status snb_evaluate_group_forces(snb_handle h, const snb_group_force_batch* b);
 
+/* -- group-pair interaction energy matrix over stored frames, direct space ---------------------- */
+/* How much group g interacts with group h, frame by frame -- contact-energy maps, interaction networks, a per-residue-pair decomposition
+ * -- without a subset (and a PME mesh) per residue: the call takes its own labelling group_of_atom[n_atoms] (USER order, values -1 or
+ * 0 .. G - 1; -1: in no group), independent of the engine's subsets, and fills
+ *     pair_energies[f][slice(g, h)][t],     slice(g, h) = max (max + 1) / 2 + min,     t = 0 Coulomb, 1 vdW
+ * -- the engine's own slice indexing with G in place of n_subsets, P = G (G + 1) / 2 rows per frame.  An entry is the RAW DIRECT-SPACE
+ * energy summed over the unordered atom pairs {i, j} with labels {g, h}, each pair once (g == h included): not scaled by the lambdas and
+ * independent of them, with the effective parameters (base values + offsets at the current global parameters).  Attributed: pairs inside
+ * the cutoff (diagonal tiles included), the Ewald exclusion corrections (the LJPME dispersion part into t = 1) and the 1-4 exceptions --
+ * exactly what an energy-only step with include_direct = 1, include_reciprocal = 0 puts into its slice energies when no
+ * dispersion-correction coefficients are set, had every atom's subset been its label.  A pair with an unlabelled end adds nothing.
+ * DIRECT SPACE ONLY: the Ewald self term, the neutralising background and the mesh (or k-vector) sum belong to the reciprocal part and are
+ * NOT in the matrix, and neither is the long-range dispersion correction; for PME and LJPME the matrix is the short-range part, as the
+ * energy groups of other MD codes.  (The reciprocal part of a group-pair matrix needs per-group structure factors and a Gram sum over the
+ * mesh: out of scope.  The full energy of a group with a SUBSET is snb_evaluate_group_energies.)  Because nothing reciprocal is
+ * attributed the call works with every method, SNB_Ewald included.
+ * With frames given the call follows the contract of snb_evaluate_frames: everything is checked before anything is enqueued; the list of
+ * frame f + 1 is built beside the pass of frame f, or in line, by the same rules; host frames go through the pinned staging; host output
+ * costs one synchronisation, at the end; device output is complete in stream order; afterwards positions, box, lambdas and mask are the
+ * caller's and the next snb_execute rebuilds; no step graph is captured or updated; frame steps count in snb_stats.n_rebuilds and in no
+ * timer; snb_get_frame_stats counts the batch and its frames.  With positions == NULL (n_frames must be 1) it is ONE evaluation of the
+ * engine's current box and positions and behaves as snb_evaluate_atom_energies behaves, a bound context included.
+ * In both forms it writes ONLY its output: the forces (snb_get_forces), the buffer of snb_set_force_output, a binding's buffers and the
+ * engine's slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) stay bit for bit what they were.  Every entry of the
+ * output is written; rows of empty groups are zeros.  The sums are accumulated per wave and added to the matrix with double atomics:
+ * equal from call to call up to the rounding of the sums, not bit for bit, in every precision mode.
+ * NULL batch, handle, group_of_atom or pair_energies, n_groups outside 1 .. 4096, a label outside [-1, G) (snb_last_error names the
+ * atom), a negative n_frames, positions == NULL with n_frames != 1: SNB_ERR_INVALID_ARGUMENT.  shard_count > 1: SNB_ERR_UNSUPPORTED.
+ * n_frames == 0 (after these checks): SNB_OK, no work.  Frames given while a context is bound: SNB_ERR_STATE.  Box errors: as
+ * snb_evaluate_frames, with the frame index.  The cap of 4096 groups keeps a frame's row at 134 MB and the key arithmetic in 32 bits: a
+ * design limit.  The working memory (the labels in sorted order, one double [P][2] matrix -- held in up to 64 copies while that stays below
+ * 512 KB) is allocated at the first call.  Host output is staged on the device in one piece, n_frames * P * 16 bytes, before the one
+ * transfer at the end: at G = 4096 a frame is 134 MB, so size n_frames to the device's memory (an allocation that fails is SNB_ERR_HIP),
+ * or take device output. */
+typedef struct {
+    int32_t        n_frames;
+    const void*    positions;        /* as snb_group_batch: [F][N][3] or [F][N][4]; NULL: the engine's CURRENT box and positions (n_frames must be 1) */
+    int32_t        is_device;
+    int32_t        is_double;
+    int32_t        stride4;
+    const double*  boxes;            /* HOST [F][9], reduced form, or NULL: the engine's current box for every frame */
+    int32_t        n_groups;         /* G, 1 .. 4096 */
+    const int32_t* group_of_atom;    /* HOST [n_atoms], USER order, -1 or 0 .. G - 1 */
+    double*        pair_energies;    /* [F][G (G + 1) / 2][2] raw direct-space (Coulomb, vdW) */
+    int32_t        out_is_device;
+} snb_group_pair_batch;
+snb_status snb_evaluate_group_pair_energies(snb_handle h, const snb_group_pair_batch* b);
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

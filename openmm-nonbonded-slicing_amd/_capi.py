@@ -20,7 +20,7 @@ SYMBOLS = [
     "snb_rebuild_neighbors", "snb_execute", "snb_get_forces", "snb_set_force_output", "snb_set_shard_blocks", "snb_get_slice_energies", "snb_slice_energies_device", "snb_synchronize",
     "snb_get_pme_parameters", "snb_get_ljpme_parameters", "snb_get_stats", "snb_reset_timers", "snb_set_timing_interval", "snb_legal_grid_size", "snb_abi_version",
     "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed", "snb_evaluate_frames", "snb_get_frame_stats", "snb_evaluate_atom_energies",
-    "snb_evaluate_atom_forces", "snb_evaluate_group_energies", "snb_evaluate_group_forces",
+    "snb_evaluate_atom_forces", "snb_evaluate_group_energies", "snb_evaluate_group_forces", "snb_evaluate_group_pair_energies",
 ]
 
 SNB_OK, SNB_ERR_INVALID_ARGUMENT, SNB_ERR_HIP, SNB_ERR_BOX_TOO_SMALL, SNB_ERR_NOT_PME, SNB_ERR_STATE, SNB_ERR_UNSUPPORTED = range(7)
@@ -87,6 +87,16 @@ class SnbGroupForceBatch(ctypes.Structure):
         ("n_groups", ctypes.c_int32), ("group_start", ctypes.POINTER(ctypes.c_int32)), ("group_atoms", ctypes.POINTER(ctypes.c_int32)),
         ("group_forces", ctypes.c_void_p), ("out_is_device", ctypes.c_int32), ("n_states", ctypes.c_int32),
         ("state_lambdas", ctypes.POINTER(ctypes.c_double)), ("state_forces", ctypes.c_void_p),
+    ]
+
+
+class SnbGroupPairBatch(ctypes.Structure):
+    """snb_group_pair_batch: a labelling of the atoms over F stored frames (or the current state) for snb_evaluate_group_pair_energies
+    (include/snb.h)."""
+    _fields_ = [
+        ("n_frames", ctypes.c_int32), ("positions", ctypes.c_void_p), ("is_device", ctypes.c_int32), ("is_double", ctypes.c_int32),
+        ("stride4", ctypes.c_int32), ("boxes", ctypes.POINTER(ctypes.c_double)), ("n_groups", ctypes.c_int32),
+        ("group_of_atom", ctypes.POINTER(ctypes.c_int32)), ("pair_energies", ctypes.c_void_p), ("out_is_device", ctypes.c_int32),
     ]
 
 
@@ -159,6 +169,7 @@ def lib():
     L.snb_evaluate_atom_forces.argtypes = [vp, i32, i32, vp, i32]        # (the same)
     L.snb_evaluate_group_energies.argtypes = [vp, ctypes.POINTER(SnbGroupBatch)]
     L.snb_evaluate_group_forces.argtypes = [vp, ctypes.POINTER(SnbGroupForceBatch)]
+    L.snb_evaluate_group_pair_energies.argtypes = [vp, ctypes.POINTER(SnbGroupPairBatch)]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError if the header and the library ever diverge
     _lib = L

@@ -523,6 +523,96 @@ class HipCalcSlicedNonbondedForceKernel:
         self._check(self._lib.snb_evaluate_group_energies(self._h, ctypes.byref(b)))
         return out
 
+    @staticmethod
+    def groupPairIndex(g, h):
+        """Row of the group pair (g, h) in a group-pair matrix: max (max + 1) / 2 + min, the slice indexing with the labels as subsets."""
+        g, h = int(g), int(h)
+        if g < 0 or h < 0:
+            raise OpenMMException("groupPairIndex: labels must not be negative")
+        return g * (g + 1) // 2 + h if g > h else h * (h + 1) // 2 + g
+
+    @staticmethod
+    def groupPairMatrix(rows, numGroups):
+        """Rows [..., P, 2] of computeGroupPairEnergies (P = G (G + 1) / 2) as the symmetric [..., G, G, 2]: entry [g][h] = [h][g] = the
+        energy of the pairs with labels {g, h}; the diagonal holds the energy inside a group, once."""
+        rows = np.asarray(rows); G = int(numGroups)
+        if rows.ndim < 2 or rows.shape[-2:] != (G * (G + 1) // 2, 2):
+            raise OpenMMException("groupPairMatrix: rows must be [..., %d, 2] for %d groups" % (G * (G + 1) // 2, G))
+        g, h = np.tril_indices(G)      # (row-major lower triangle: g (g + 1) / 2 + h, the order of the rows)
+        out = np.zeros(rows.shape[:-2] + (G, G, 2), dtype=rows.dtype)
+        out[..., g, h, :] = rows
+        out[..., h, g, :] = rows
+        return out
+
+    @staticmethod
+    def labelsFromGroups(groups, numAtoms):
+        """Disjoint lists of atom indices, one per group, as the label array of computeGroupPairEnergies: int32 [numAtoms], label g on the
+        atoms of list g, -1 on atoms in no list.  An atom in two lists (or twice in one) is refused: a label array cannot say it."""
+        labels = np.full(int(numAtoms), -1, dtype=np.int32)
+        for g, lst in enumerate(groups):
+            for a in np.asarray(list(lst), dtype=np.int64).reshape(-1):
+                if a < 0 or a >= numAtoms:
+                    raise OpenMMException("labelsFromGroups: group %d: atom index %d is outside [0, %d)" % (g, a, numAtoms))
+                if labels[a] != -1:
+                    raise OpenMMException("labelsFromGroups: atom %d is listed twice (groups %d and %d): the groups must be disjoint" % (a, labels[a], g))
+                labels[a] = g
+        return labels
+
+    def _groupPairBatch(self, labels, numGroups):
+        lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        if lab.shape[0] != self.numParticles:
+            raise OpenMMException("group-pair energies: one label per atom (%d), -1 for atoms in no group" % self.numParticles)
+        G = int(numGroups) if numGroups is not None else int(lab.max()) + 1 if lab.size else 0
+        if G < 1:
+            raise OpenMMException("group-pair energies: at least one group")
+        b = _capi.SnbGroupPairBatch()
+        b.n_groups = G; b.group_of_atom = _ip(lab)
+        return b, lab      # (the array the batch points into: the caller keeps it until the call has returned)
+
+    def computeGroupPairEnergies(self, context, labels, numGroups=None, devicePointer=None):
+        """Group-pair interaction energy matrix at the context's positions, box and parameters (include/snb.h,
+        snb_evaluate_group_pair_energies with positions == NULL): labels[i] in -1, 0 .. G - 1 is the group of atom i (-1: none; the
+        labelling is the call's own, independent of the force's subsets), the result (G (G + 1) / 2, 2) holds the raw Coulomb and vdW
+        energy of the atom pairs with labels {g, h} in row groupPairIndex(g, h) -- groupPairMatrix gives the symmetric (G, G, 2).  DIRECT
+        SPACE ONLY: pairs inside the cutoff, Ewald exclusion corrections and 1-4 exceptions; with PME / LJPME / Ewald that is the
+        short-range part (the reciprocal sum, the self term, the background and the dispersion correction are not attributed to group
+        pairs), which is why every method is served.  numGroups: G (default: the largest label + 1; at most 4096).  devicePointer: address
+        of a double [G (G + 1) / 2][2] array on the engine's device that takes the result (complete in stream order); then None is returned."""
+        self._push_state(context)
+        b, keep = self._groupPairBatch(labels, numGroups)
+        b.n_frames = 1
+        out = None
+        if devicePointer is not None:
+            b.pair_energies = ctypes.c_void_p(int(devicePointer)); b.out_is_device = 1
+        else:
+            out = np.zeros((b.n_groups * (b.n_groups + 1) // 2, 2))
+            b.pair_energies = out.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        self._check(self._lib.snb_evaluate_group_pair_energies(self._h, ctypes.byref(b)))
+        return out
+
+    def computeGroupPairEnergiesForFrames(self, context, labels, positions=None, boxes=None, numGroups=None, positionsDevicePointer=None, numFrames=None,
+                                          devicePointer=None):
+        """The group-pair matrix [F][G (G + 1) / 2][2] of F stored frames in one call (include/snb.h, snb_evaluate_group_pair_energies): a
+        contact-energy map or residue-residue interaction network over a trajectory -- the frame pipeline of computeSliceEnergiesForFrames
+        with the group-pair pass as its step.  Direct space only, as computeGroupPairEnergies.  labels, numGroups: as there.  positions,
+        boxes, positionsDevicePointer, numFrames: as in computeSliceEnergiesForFrames.  devicePointer: address of a double
+        [F][G (G + 1) / 2][2] array on the engine's device that takes the result (complete in stream order); then None is returned.
+        Parameters are pushed from the context first; the context's own positions, the forces and the slice energies of the last steps
+        stay as they are."""
+        self._push_frame_state(context)
+        b, keep = self._groupPairBatch(labels, numGroups)
+        if positions is None and positionsDevicePointer is None:
+            raise OpenMMException("computeGroupPairEnergiesForFrames: positions or positionsDevicePointer must be given (computeGroupPairEnergies evaluates the context's own state)")
+        F, frames = self._frames_into(b, "computeGroupPairEnergiesForFrames", positions, boxes, positionsDevicePointer, numFrames)
+        out = None
+        if devicePointer is not None:
+            b.pair_energies = ctypes.c_void_p(int(devicePointer)); b.out_is_device = 1
+        else:
+            out = np.zeros((F, b.n_groups * (b.n_groups + 1) // 2, 2))
+            b.pair_energies = out.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        self._check(self._lib.snb_evaluate_group_pair_energies(self._h, ctypes.byref(b)))
+        return out
+
     def _groupForceOutputs(self, b, F, lambdaStates, keep):
         """Host outputs of a group-force batch: rows (F, G, n_subsets, 2, 3) and, with lambdaStates [K][S][2], stateForces (F, K, G, 3)."""
         rows = np.zeros((F, b.n_groups, self.numSubsets, 2, 3))
@@ -705,6 +795,9 @@ class SlicedNonbondedForceImpl:
     def getGroupForces(self, context, groups, **options):
         return self.kernel.computeGroupForces(context, groups, **options)
 
+    def getGroupPairEnergies(self, context, labels, **options):
+        return self.kernel.computeGroupPairEnergies(context, labels, **options)
+
 
 class System:
     def __init__(self):
@@ -819,6 +912,16 @@ class Context:
         for impl in self._impls:
             if impl.owner is force:
                 return impl.getGroupForces(self, groups, **options)
+        raise OpenMMException("force not in this context")
+
+    def getGroupPairEnergies(self, force, labels, **options):
+        """Group-pair interaction energy matrix of ``force`` (direct space), (G (G + 1) / 2, 2) for the labelling ``labels``:
+        HipCalcSlicedNonbondedForceKernel.computeGroupPairEnergies."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        for impl in self._impls:
+            if impl.owner is force:
+                return impl.getGroupPairEnergies(self, labels, **options)
         raise OpenMMException("force not in this context")
 
     def getAtomForces(self, force, **options):

@@ -5,8 +5,8 @@
 // table in user order.  Analysis kernels beside the step kernels: they share the lists, the tiles and the parameter structs of
 // direct.hip / pme.hip and the energy expressions of the energy-only kernels, and write nothing a step reads.
 //
-//   PairEnergy                      what a tile pair, a 1-4 exception and an Ewald exclusion correction add to the table.  The walkers that
-//                                   call it are shared with the force table and live in atom_table.h:
+//   PairEnergy                      what a tile pair, a 1-4 exception and an Ewald exclusion correction add to the table (pair_energy.h: shared
+//                                   with the group-pair matrix).  The walkers that call it are shared with the force table and live in atom_table.h:
 //   k_atomTiles<.., PairEnergy>     the tiles of the pair kernel and, in its first work-groups, the two pair lists; the j-side LDS region is [32][2];
 //   k_atomStencil<.., GRAD = false> q_i psi_J(r_i) for every held mesh J from the UNMIXED potentials: the value part of the interpolation.
 //   k_atomFinish     twice the Ewald self terms into column s_i, the neutralising background -2 c q_i Q_J, sorted -> user order.
@@ -14,90 +14,11 @@
 //   k_groupCombine   lists one thread per (group, subset), long lists one wave per chunk and a second launch that adds a group's chunks
 //                    in list order -- no atomics, so a group's row is a function of the working table alone.
 #include "atom_table.h"
+#include "pair_energy.h"
 #include <algorithm>
 #include <vector>
 
 namespace snb {
-
-// raw pair energies of (i, j) as the energy instantiation of tileSteps (direct.hip) forms them; returns whether the pair is inside the cutoff
-template <typename Real, int MC, bool WRAP>
-__device__ __forceinline__ bool pairEnergies(const DirectParams<Real>& p, const typename Vec<Real>::T4 pi, const typename Vec<Real>::T2 sei, const Real qi, const Real c6i,
-                                             const typename Vec<Real>::T4 xj, const typename Vec<Real>::T2 sj2, Real& eC, Real& eLJ) {
-    Real dx = pi.x - xj.x, dy = pi.y - xj.y, dz = pi.z - xj.z;
-    if (WRAP) wrapDelta<Real>(dx, dy, dz, p.box, p.invBoxDiag);
-    const Real r2 = dx * dx + dy * dy + dz * dz;
-    const Real invR = rsq(r2);
-    const Real r = r2 * invR;
-    const bool include = MC == MC_NOCUTOFF ? true : (r2 < p.cutoff2);
-    // Lennard-Jones (sigeps holds sigma/2 and 2 sqrt(eps))
-    const Real sig = sei.x + sj2.x;
-    Real s2 = sig * invR; s2 *= s2;
-    const Real s6 = s2 * s2 * s2;
-    eLJ = sei.y * sj2.y * s6 * (s6 - Real(1));
-    if (MC == MC_LJPME) {      // multiplicative grid term + potential shifts
-        const Real dar2 = p.alphaD * p.alphaD * r2, dar4 = dar2 * dar2;
-        const Real invR2 = invR * invR;
-        const Real c6 = c6i * (Real(8) * sj2.x * sj2.x * sj2.x * sj2.y);
-        const Real coef = invR2 * invR2 * invR2 * c6;
-        const Real expd = fexp(-dar2);
-        const Real epre = Real(1) + dar2 + Real(0.5) * dar4;
-        Real sg2 = sig * sig; const Real sg6 = sg2 * sg2 * sg2 * p.invCut6;
-        eLJ += coef * (Real(1) - expd * epre) + sei.y * sj2.y * (Real(1) - sg6) * sg6 - c6 * p.multShift6;
-    } else if (MC != MC_NOCUTOFF) {
-        if (p.useSwitch && r > p.switchDist) {
-            const Real tt = (r - p.switchDist) * p.invSwitchWidth;
-            eLJ *= Real(1) + tt * tt * tt * (Real(-10) + tt * (Real(15) - tt * Real(6)));
-        }
-    }
-    const Real qq = qi * xj.w;
-    if ((MC == MC_EWALD || MC == MC_LJPME) && sizeof(Real) == 4 && (p.ewUsePoly & SNB_POLY_ENERGY)) {
-        // single precision: qq (1/r - Et(r^2)), Et = erf(ar)/r as the degree-13 polynomial of the packed energy kernels -- the error of the
-        // Abramowitz & Stegun erfc is one-signed and an atom's column sums thousands of pairs whose direct and reciprocal parts cancel
-        const Real t = r2 * p.ewScale - Real(1);
-        Real et = p.ewPolyE[13];
-#pragma unroll
-        for (int k = 12; k >= 0; k--) et = et * t + p.ewPolyE[k];
-        eC = qq * (invR - et);
-    } else if (MC == MC_EWALD || MC == MC_LJPME) {
-        const Real ar = p.alpha * r;
-        eC = qq * invR * erfcFromExp(ar, expNegAlpha2R2(p.alpha2l2e, p.alpha, r2));
-    } else if (MC == MC_RF) eC = qq * (invR + p.krf * r2 - p.crf);
-    else eC = qq * invR;
-    return include;
-}
-
-// the energy table's contributions to the shared walkers (atom_table.h): two values per pair, Coulomb and vdW
-struct PairEnergy {
-    static constexpr int NV = 2, UNROLL = 4, J_SIGN = 1;
-    template <typename Real, int MC, bool WRAP>
-    static __device__ __forceinline__ bool eval(const DirectParams<Real>& p, const typename Vec<Real>::T4 pi, const typename Vec<Real>::T2 sei, const Real qi, const Real c6i,
-                                                const typename Vec<Real>::T4 xj, const typename Vec<Real>::T2 sj2, Real* v) {
-        return pairEnergies<Real, MC, WRAP>(p, pi, sei, qi, c6i, xj, sj2, v[0], v[1]);
-    }
-    // 1-4 exceptions: the energies of exceptionsBody (direct.hip)
-    template <typename Real, typename Par> static __device__ __forceinline__ void exception(const Par par, const Real dx, const Real dy, const Real dz, const Real invR, const Real s6, double* v) {
-        v[0] = par.z * invR; v[1] = par.y * (s6 - Real(1)) * s6;
-    }
-    // Ewald exclusion corrections: the energies of exclusionAtomsBody (direct.hip; formed in double as there)
-    template <typename Real>
-    static __device__ __forceinline__ void exclusion(const PairListParams<Real>& p, const Real qa, const Real qb, const typename Vec<Real>::T2 sei, const int b, const Real dx, const Real dy, const Real dz, double* v) {
-        const double rd = sqrt((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
-        const double qqd = (double)qa * (double)qb * SNB_ONE_4PI_EPS0;
-        const double erfv = erf(p.alpha64 * rd);
-        v[0] = erfv > 1e-6 ? -qqd * erfv / rd : -p.alpha64 * 1.1283791670955126 * qqd;
-        v[1] = 0;
-        if (p.ljpme) {
-            const Real r2 = dx * dx + dy * dy + dz * dz;
-            const Real invR = Real(1) / sqrt(r2);
-            const auto sej = p.sigeps[b];
-            const Real c6i = Real(8) * sei.x * sei.x * sei.x * sei.y;
-            const Real c6 = c6i * (Real(8) * sej.x * sej.x * sej.x * sej.y);
-            const Real dar2 = p.alphaD * p.alphaD * r2, dar4 = dar2 * dar2;
-            const Real invR2 = invR * invR;
-            v[1] = (double)(c6 * invR2 * invR2 * invR2 * (Real(1) - fexp(-dar2) * (Real(1) + dar2 + Real(0.5) * dar4)));
-        }
-    }
-};
 
 template <typename Real> void launchAtomPairs(const DirectParams<Real>& p, int mc, bool wrap, const PairListParams<Real>* lists, double* tab, hipStream_t s) { launchAtomTiles<Real, PairEnergy>(p, mc, wrap, lists, tab, s); }
 template void launchAtomPairs<float>(const DirectParams<float>&, int, bool, const PairListParams<float>*, double*, hipStream_t);

@@ -124,6 +124,7 @@ struct EngineBase {
     virtual void evaluateAtomTable(bool forces, int, int, double*, int) = 0;
     virtual void evaluateGroupEnergies(const snb_group_batch*) = 0;
     virtual void evaluateGroupForces(const snb_group_force_batch*) = 0;
+    virtual void evaluateGroupPairEnergies(const snb_group_pair_batch*) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
@@ -2095,6 +2096,74 @@ public:
             });
     }
 
+    // ------------------------------------------------------------------------------------------
+    // Group-pair interaction energy matrix, direct space (snb_evaluate_group_pair_energies): the raw energies of the
+    // tiles and of the two pair lists under slice(label_i, label_j) of the caller's G labels, per frame.  The frame, the refusals and the
+    // neighbour-list rules of evaluateGroups above, with a step of its own: gather, zero fill, label gather, the tile launch of grouppairs.hip
+    // with the direct parameters of the atom pass, the copy to the frame's row.  No PME call at all; any method, classic Ewald included.
+    // Writes only its output: the labels (user and sorted order), the working matrix and the staging of a host result are its own.
+    // ------------------------------------------------------------------------------------------
+    DevBuf<int> dPairLabels, dPairLabelsSorted; DevBuf<double> groupPairTab, groupPairOut;
+    void evaluateGroupPairEnergies(const snb_group_pair_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::string who = "snb_evaluate_group_pair_energies";
+        const int G = b->n_groups, F = b->n_frames;
+        const FrameInput in{"snb_evaluate_group_pair_energies", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
+        // ---- everything is checked before anything is enqueued or changed
+        if (!b->group_of_atom || !b->pair_energies) { err = who + ": group_of_atom and pair_energies must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (G < 1 || G > 4096) { err = who + ": n_groups must lie in 1 .. 4096"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        for (int i = 0; i < N; i++) {
+            const int l = b->group_of_atom[i];
+            if (l < -1 || l >= G) { err = who + ": atom " + std::to_string(i) + ": label " + std::to_string(l) + " is outside [-1, " + std::to_string(G) + ")"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        }
+        if (F < 0) { err = who + ": negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (cfg.shard_count > 1) { err = who + ": not available on sharded engines (a rank holds a part of the lists)"; throw (int)SNB_ERR_UNSUPPORTED; }
+        if (F == 0) return;
+        if (!in.positions && F != 1) { err = who + ": positions == NULL evaluates the engine's current state: n_frames must be 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (in.positions && ctx.on) { err = who + ": frames were given while a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        if (in.positions) checkFrames(in, false);
+        const size_t rowLen = (size_t)G * (G + 1) / 2 * 2;
+        // a small matrix is kept in copies (up to 64, 512 KB in all), a work-group adding into its own: few rows are hot rows
+        int parts = 64;
+        while (parts > 1 && parts * rowLen > 65536) parts >>= 1;
+        const bool hostOut = b->out_is_device == 0;
+        double* rows = b->pair_energies;
+        auto prepare = [&]() {      // the labels: one upload per call, through the pinned ring
+            pinned.upload(dPairLabels, std::vector<int>(b->group_of_atom, b->group_of_atom + N), stream);
+            groupPairTab.resize(parts * rowLen);
+            if (hostOut) { groupPairOut.resize((size_t)F * rowLen); rows = groupPairOut.p; }
+        };
+        auto pass = [&](int f, int npad) {
+            dPairLabelsSorted.resize((size_t)npad);
+            (void)enqueueGather(false, false, false, 0);      // sorted positions, the displacement watch; nothing cleared
+            launchZeroFill(groupPairTab.p, sizeof(double) * parts * rowLen, stream);
+            launchGroupPairLabels(dPairLabels.p, dSortedToUser.p, Npad, dPairLabelsSorted.p, stream);      // (reads this frame's list set: before evFrameStep[f & 1])
+            const int* const need = sliceNeed(StepEnergy::All);
+            DirectParams<Real> p; PairListParams<Real> q;
+            std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
+            fillDirect(p, need); fillPairLists(q, need);
+            launchGroupPairTiles<Real>(p, methodClass(), wrapMode, &q, dPairLabelsSorted.p, groupPairTab.p, parts, rowLen, stream);
+            launchGroupPairFinish(groupPairTab.p, rowLen, parts, rows + (size_t)f * rowLen, stream);
+        };
+        auto deliver = [&]() {
+            if (!hostOut) return false;
+            HIPCHECK(hipMemcpyAsync(b->pair_energies, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+            return true;
+        };
+        if (!in.positions) {      // the engine's current state, as the atom calls take it
+            beginExecute(false, 0);
+            prepare();
+            pass(0, Npad);
+            endExecute();
+            deliver();
+            return;
+        }
+        prepare();
+        // (the sorted labels are sized by the batch's padded-count prediction, in force from the first frame's build on: no allocation while a side build is in flight)
+        runFrames(in, t0, [&](int f) { pass(f, std::max(Npad, npadPredict)); }, deliver);
+    }
+
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
     void runEwald(bool energy, bool forces) {
         if (hKvec.empty()) {
@@ -2345,6 +2414,10 @@ snb_status snb_evaluate_group_energies(snb_handle h, const snb_group_batch* b) {
 snb_status snb_evaluate_group_forces(snb_handle h, const snb_group_force_batch* b) {
     if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_forces: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
     return guard(h, [&] { h->impl->evaluateGroupForces(b); });
+}
+snb_status snb_evaluate_group_pair_energies(snb_handle h, const snb_group_pair_batch* b) {
+    if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_pair_energies: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
+    return guard(h, [&] { h->impl->evaluateGroupPairEnergies(b); });
 }
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 

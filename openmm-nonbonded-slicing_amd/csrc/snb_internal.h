@@ -347,6 +347,14 @@ void launchAtomForceFinish(const double* tab, const int* userToSorted, int nAtom
 // asked for) and, with nStates > 0, states[nStates][G][3] = the rows contracted per atom with stateLambdas[nStates][S][2] (device)
 void launchGroupForceFinish(const double* tab, const int* userToSorted, const int* blockSubset, int nsub, const GroupPlan& plan, const int* packed, const double* stateLambdas, int nStates,
                             double* partial /* [nChunks][(rows ? nsub * 6 : 0) + nStates * 3] */, double* rows, double* states, hipStream_t s);
+// group-pair energy matrix, direct space (grouppairs.hip, snb_evaluate_group_pair_energies): labelSorted[nPad] from the caller's labels in
+// user order (-1 on padding slots); M = double [G (G + 1) / 2][2], added to, under slice(label_i, label_j) of every pair of the tiles and of
+// the two pair lists; the finish copies M to a row of the output
+void launchGroupPairLabels(const int* labelsUser, const int* sortedToUser, int nPad, int* labelSorted, hipStream_t s);
+// M is held in `parts` copies (a power of two), `stride` doubles apart: a work-group adds into copy blockIdx mod parts, the finish adds the copies
+template <typename Real> void launchGroupPairTiles(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, const int* labelSorted, double* M, int parts,
+                                                   size_t stride, hipStream_t s);
+void launchGroupPairFinish(const double* M, size_t n, int parts, double* row, hipStream_t s);
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s);   // 1: forward z FFT already done; 2: ... and the spectrum is plane-major (plane path)
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s);   // rebuild time: fills the plane path's kernel-value table
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s);   // after a spreader that returned 2: k_planeXY + k_fftZInvMix instead of forward FFT, convolution, inverse FFT
