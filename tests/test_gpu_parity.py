@@ -204,7 +204,7 @@ FORCE_ONLY_CASES = [
     # name, n, nsub, method, L, pme, ljpme, switch
     ("pme_13824_n4", 13824, 4, 4, 6.0, (2.6283, 48, 48, 48), None, False),        # packed pair kernel (polynomial Ewald), brick PME, graph replay
     ("rf_13824_n3", 13824, 3, 2, 6.0, None, None, False),                         # packed pair kernel, reaction field
-    ("rf_switch_13824_n2", 13824, 2, 2, 6.0, None, None, True),                   # switching function: scalar forces-only kernel
+    ("rf_switch_13824_n2", 13824, 2, 2, 6.0, None, None, True),                   # switching function: the packed kernel's SWITCH instantiation in single and mixed precision (direct.hip directKernel), the scalar tile kernel in double
     ("ljpme_13824_n3", 13824, 3, 5, 6.0, (2.6283, 48, 48, 48), (2.6283, 24, 24, 24), False),
     ("pme_smallbox_4096_n2", 4096, 2, 4, 3.5, (2.6283, 32, 32, 32), None, False),  # host-built lists, atomic spreader
 ]
