@@ -18,6 +18,7 @@
 #include "pair_math.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -82,19 +83,24 @@ template <typename P> __device__ inline bool cuResident(const P& p) {
 // k, k + SNB_WORK_SHARDS, ... (the list is sorted longest first, so every counter's sequence is too).  One counter for all waves serialises
 // at ~15 ns per claim (same-address device-scope atomics: 28 768 claims = 0.44 ms, measured) -- sixteen are far below that rate.
 // A wave starts at a home counter and, once that one is exhausted, reads all counters in one load and moves to the next one with items left.
-struct WorkClaim {
+// FRESH: the counters' per-lane address is formed where it is used (the rare path of an exhausted counter) instead of being held in two
+// registers for the whole kernel -- the derivative kernel, which has none to spare (k_directPackedSelected).
+template <bool FRESH = false> struct WorkClaim {
     int* ctr; int numWork, shard, lane;
+    __device__ int myLane() const { int l = lane; if constexpr (FRESH) asm volatile("" : "+v"(l)); return l; }
     __device__ int issue() const { int v = 0; if (lane == 0) v = atomicAdd(&ctr[shard * 32], 1); return v; }      // lane 0 holds the claim
     __device__ bool anyLeft() const {      // (one load of all counters: a launch that arrives when everything is claimed leaves after one round trip)
         int left = 0;
-        if (lane < SNB_WORK_SHARDS) left = (numWork - lane + SNB_WORK_SHARDS - 1) / SNB_WORK_SHARDS - __hip_atomic_load(&ctr[lane * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int l = myLane();
+        if (l < SNB_WORK_SHARDS) left = (numWork - l + SNB_WORK_SHARDS - 1) / SNB_WORK_SHARDS - __hip_atomic_load(&ctr[l * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return __ballot(left > 0) != 0;
     }
     __device__ int resolve(int v) {      // item index of a claim issued on `shard`, moving on to other counters when that one has run out; numWork: no items left
         int idx = shard + SNB_WORK_SHARDS * __builtin_amdgcn_readfirstlane(v);
         while (idx >= numWork) {
             int left = 0;
-            if (lane < SNB_WORK_SHARDS) left = (numWork - lane + SNB_WORK_SHARDS - 1) / SNB_WORK_SHARDS - __hip_atomic_load(&ctr[lane * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int l = myLane();
+            if (l < SNB_WORK_SHARDS) left = (numWork - l + SNB_WORK_SHARDS - 1) / SNB_WORK_SHARDS - __hip_atomic_load(&ctr[l * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned m = (unsigned)__ballot(left > 0);
             if (m == 0) return numWork;
             const int from = (shard + 1) & (SNB_WORK_SHARDS - 1);
@@ -106,6 +112,17 @@ struct WorkClaim {
     }
 };
 
+
+// A field of the kernel's FIRST argument, read from the kernel-argument segment behind a barrier the compiler cannot move the load across.
+// Kernel arguments are scalar loads the compiler hoists to the kernel's entry and keeps in SGPRs for the whole kernel; what only a rare
+// path reads (the derivative kernel's energy polynomial, 14 coefficients, and its energy partition) then pushes the tile loop over the
+// scalar register file, and every trip reloads spilled SGPRs with v_readlane.  Through this the rare path loads its constants itself.
+#define SNB_KERNARG __attribute__((address_space(4)))
+template <typename T> __device__ __forceinline__ const SNB_KERNARG T* kernargField(size_t offset) {
+    const SNB_KERNARG char* k = (const SNB_KERNARG char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return (const SNB_KERNARG T*)(k + offset);
+}
 
 // ---- cross-lane helpers -------------------------------------------------------------------------
 // DPP row_ror:1 -- every 16-lane row rotates by one lane (lane c receives the value of lane (c-1)&15).
@@ -270,7 +287,7 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 8 ? SNB_DIRECT_F64_WAVES : 4)
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool dyn = p.workCounter != nullptr;
-    WorkClaim wc{p.workCounter, p.numWork, (tileBlock * 4 + wid) & (SNB_WORK_SHARDS - 1), lane};
+    WorkClaim<> wc{p.workCounter, p.numWork, (tileBlock * 4 + wid) & (SNB_WORK_SHARDS - 1), lane};
     int item = tileBlock * 4 + wid;
     if (dyn) item = wc.anyLeft() ? wc.resolve(wc.issue()) : p.numWork;
     for (; item < p.numWork; ) {   // no block-level barrier inside the loop
@@ -401,13 +418,15 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 8 ? SNB_DIRECT_F64_WAVES : 4)
 // Staging: entry e (0..15) of quarter r holds atom 8r + (e & 7), so the rotated read index (c & 7) + 8 - s needs no wrap.
 // ENERGY: the raw (unscaled) pair energies of the tile's slice are accumulated as well -- eLJ = eps_ij s6 (s6 - 1) and the Coulomb
 // energy of the method (Ewald: qq erfc(ar)/r with the A&S erfc) -- from the
-// RAW i-parameters qiRaw / epsiRaw, while the forces keep using the lambda-scaled ones.  This is the kernel of every step of a force
-// that asks for energy-parameter derivatives (the reference accumulates them whether or not the energy is requested, Q4).
-template <int MC, bool MASKED, bool POLY, bool ENERGY, bool SWITCH, bool FORCES = true>      // FORCES == false: energies alone, as tileSteps
-__device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, const float4* rdPos, const float2* rdSe, const v2f pix, const v2f piy, const v2f piz,
+// RAW i-parameters qiRaw / epsiRaw, while the forces keep using the lambda-scaled ones.  A force that asks for energy-parameter
+// derivatives needs them on every step (the reference accumulates them whether or not the energy is requested, Q4): those steps run
+// the energy body on the tiles of the wanted slices alone (directPackedBody, E_TILES).
+// EPOLY: p.ewPolyE, or the same coefficients through kernargField (below) where only a few tiles of a launch want energies.
+template <int MC, bool MASKED, bool POLY, bool ENERGY, bool SWITCH, bool FORCES = true, typename EPOLY = const float*, int UNROLL = 4>      // FORCES == false: energies alone, as tileSteps
+__device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, const EPOLY ewPolyE, const float4* rdPos, const float2* rdSe, const v2f pix, const v2f piy, const v2f piz,
                                                 const v2f sigi, const v2f qiS, const v2f epsiS, const v2f qiRaw, const v2f epsiRaw, const v2f c6iRaw, const float lamL, const unsigned maskA, const unsigned maskB, const int c,
                                                 v2f& fix, v2f& fiy, v2f& fiz, float& fjx, float& fjy, float& fjz, v2f& ecl, v2f& elj) {
-#pragma unroll 4
+#pragma unroll UNROLL
     for (int s = 0; s < 8; s++) {
         const float4 xj = rdPos[-s];
         const float2 sj = rdSe[-s];
@@ -468,9 +487,9 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
                 // 1.5e-7 absolute, but its error is one-signed over most of the range and qq erfc(ar)/r is summed over 6e7 pairs: +1.0 kJ/mol
                 // on the water-water slice of the 96k-atom box, whose direct (6.5e6) and reciprocal (-6.5e6) parts cancel to 788 -- 1.3e-3.
                 // Degree 13 leaves a tenth of that (tools/erfc_energy_check.py; degree 11 is worse than A&S, beyond 13 float coefficients limit it).
-                v2f et = t * p.ewPolyE[13] + p.ewPolyE[12];
+                v2f et = t * ewPolyE[13] + ewPolyE[12];
 #pragma unroll
-                for (int k = 11; k >= 0; k--) et = et * t + p.ewPolyE[k];
+                for (int k = 11; k >= 0; k--) et = et * t + ewPolyE[k];
                 eC = qqRaw * (invR - et);
             }
         } else if (MC == MC_EWALD || MC == MC_LJPME) {
@@ -511,8 +530,22 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
 
 // The first nListBlocks work-groups of the launch run the O(N) pair lists (exclusion corrections, then 1-4 exceptions: latency-bound
 // work that overlaps the VALU-bound tile work instead of trailing it as a launch of its own); the others loop over tile work items.
-template <int MC, bool POLY, bool ENERGY, bool SWITCH, bool FIXED>
-__global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
+//
+// Energy bookkeeping of the tile loop (EMODE):
+//   E_RUNS  (include_energy == 1, every slice wanted): ecl/elj live across the tiles of a work item and are reduced when the slice changes
+//           -- one wave reduction per RUN of tiles; a reduction per tile would cost these steps about 15 %.
+//   E_TILES (include_energy == 2, derivative steps: the slices of snb_set_energy_slices, a few per cent of the tiles): nothing of the
+//           bookkeeping is live across a tile.  A wanted tile starts its own ecl/elj at zero and reduces them at its end (the same
+//           reduction: wave sum in double, lane 0, two atomics into the slice's partition); every other tile takes the forces kernel's
+//           path plus the wanted-or-not decision -- one dword of p.sliceNeed requested with the tile's atoms and moved to an SGPR,
+//           together with the slice, when the tile is staged.  With the run state (curSlice, curNeeded, two accumulators, the vector
+//           compare of the slices) the E_RUNS form carries across the forces path, the kernel exceeds the scalar register file and
+//           reloads spilled SGPRs with v_readlane on every trip: 27 of the 59 VALU instructions a pair of unwanted tiles cost it over
+//           the forces kernel (docs/MEASUREMENT_LOG.md, "derivative tiles").
+enum { E_NONE = 0, E_RUNS = 1, E_TILES = 2 };
+template <int MC, bool POLY, int EMODE, bool SWITCH, bool FIXED>
+__device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, const PairListParams<float>& q, const int nExclBlocks, const int nListBlocks) {
+    constexpr bool ENERGY = EMODE != E_NONE, RUNS = EMODE == E_RUNS, TILES = EMODE == E_TILES;
     const int listBlock = p.listsLast ? (int)blockIdx.x - ((int)gridDim.x - nListBlocks) : (int)blockIdx.x;      // (CU-limited launch: list blocks last, see k_direct)
     if (listBlock >= 0 && listBlock < nListBlocks) {      // (energy steps: the list bodies reduce their slice energies in 2 S doubles of dynamic LDS)
         if (listBlock < nExclBlocks) { PairListParams<float> qe = q; qe.n = q.nExclAtoms; exclusionAtomsBody<float, ENERGY>(qe, listBlock); }
@@ -538,7 +571,7 @@ __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<floa
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool dyn = p.workCounter != nullptr;      // (uniform) items through the device counters: every wave of either launch claims one at a time
-    WorkClaim wc{p.workCounter, p.numWork, (tileBlock * 4 + wid) & (SNB_WORK_SHARDS - 1), lane};
+    WorkClaim<TILES> wc{p.workCounter, p.numWork, (tileBlock * 4 + wid) & (SNB_WORK_SHARDS - 1), lane};
     int item = tileBlock * 4 + wid;
     if (dyn) item = wc.anyLeft() ? wc.resolve(wc.issue()) : p.numWork;
     for (; item < p.numWork; ) {   // no block-level barrier inside the loop
@@ -564,6 +597,12 @@ __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<floa
             if (lane == 0) { atomicAdd(&sliceE[2 * curSlice], a); atomicAdd(&sliceE[2 * curSlice + 1], b); }
         }
         ecl = {0.f, 0.f}; elj = {0.f, 0.f};
+    };
+    auto flushTile = [&](int slice, v2f e, v2f l) {   // E_TILES: the raw energies of one wanted tile, reduced as flushEnergy does
+        const double a = waveSum((double)e.x + (double)e.y), b = waveSum((double)l.x + (double)l.y);
+        const int ns = *kernargField<int>(offsetof(DirectParams<float>, nsub));
+        double* const part = SNB_SLICE_E_PARTITION(*kernargField<double*>(offsetof(DirectParams<float>, sliceE)), ns * (ns + 1));
+        if (lane == 0) { atomicAdd(&part[2 * slice], a); atomicAdd(&part[2 * slice + 1], b); }
     };
 
     float4* myPos = s_pos[wid];
@@ -618,7 +657,8 @@ __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<floa
         st.hasMask = R.maskIdx >= 0;
         st.maskA = st.hasMask ? R.mA >> (8 * row) : 0u; st.maskB = st.hasMask ? R.mB >> (8 * row) : 0u;   // my j-quarter's 8 bits
         st.lamC = R.lam.x; st.lamL = R.lam.y;
-        st.slice = R.slice & 0xFFFF;
+        if constexpr (TILES) st.slice = __builtin_amdgcn_readfirstlane(R.slice) & 0xFFFF;      // (scalar: only a wanted tile's reduction reads it)
+        else st.slice = R.slice & 0xFFFF;
         st.needE = ENERGY && __builtin_amdgcn_readfirstlane(R.need) != 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -631,13 +671,21 @@ __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<floa
     auto tile = [&](TileRegs& X, TileRegs& Y, const int t, Staged& st) {
         requestAtoms(Y);      // (issues the previous tile's j-force atomics first)
         requestList(X, t + 2 < tEnd ? t + 2 : tEnd - 1);
-        // (the sums of a slice nobody asked for are zero: no wave reduction, no atomics -- on derivative steps 95 % of the slice changes)
-        if (ENERGY && st.slice != curSlice) { if (curNeeded) flushEnergy(); curSlice = st.slice; curNeeded = st.needE; }
+        // (E_RUNS; the sums of a slice nobody asked for are zero: no wave reduction, no atomics)
+        if (RUNS && st.slice != curSlice) { if (curNeeded) flushEnergy(); curSlice = st.slice; curNeeded = st.needE; }
         const v2f qiS = qi * st.lamC, epsiS = epsi * st.lamL;      // lambda folded into the i-side parameters once per tile
         float fjx = 0, fjy = 0, fjz = 0;
-#define SNB_TILE_PACKED(M, E) tileStepsPacked<MC, M, POLY, E, SWITCH>(p, rdPos, rdSe, pix, piy, piz, sigi, qiS, epsiS, qi, epsi, c6i, st.lamL, st.maskA, st.maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj)
-        if (ENERGY && st.needE) { if (st.hasMask) SNB_TILE_PACKED(true, ENERGY); else SNB_TILE_PACKED(false, ENERGY); }
-        else { if (st.hasMask) SNB_TILE_PACKED(true, false); else SNB_TILE_PACKED(false, false); }      // forces only (also: energy steps, slice not wanted)
+#define SNB_TILE_PACKED(M, E, EP, ECL, ELJ) tileStepsPacked<MC, M, POLY, E, SWITCH>(p, EP, rdPos, rdSe, pix, piy, piz, sigi, qiS, epsiS, qi, epsi, c6i, st.lamL, st.maskA, st.maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ECL, ELJ)
+        if (TILES && st.needE) {      // a wanted tile of a derivative step: its own sums, reduced here
+            v2f te = {0.f, 0.f}, tl = {0.f, 0.f};
+            const auto ep = kernargField<float>(offsetof(DirectParams<float>, ewPolyE));
+#define SNB_TILE_WANTED(M) tileStepsPacked<MC, M, POLY, true, SWITCH, true, decltype(ep), 2>(p, ep, rdPos, rdSe, pix, piy, piz, sigi, qiS, epsiS, qi, epsi, c6i, st.lamL, st.maskA, st.maskB, c, fix, fiy, fiz, fjx, fjy, fjz, te, tl)
+            if (st.hasMask) SNB_TILE_WANTED(true); else SNB_TILE_WANTED(false);      // (two steps unrolled, not four: the kernel keeps the forces kernel's register allocation)
+#undef SNB_TILE_WANTED
+            flushTile(st.slice, te, tl);
+        }
+        else if (RUNS && st.needE) { if (st.hasMask) SNB_TILE_PACKED(true, ENERGY, p.ewPolyE, ecl, elj); else SNB_TILE_PACKED(false, ENERGY, p.ewPolyE, ecl, elj); }
+        else { if (st.hasMask) SNB_TILE_PACKED(true, false, p.ewPolyE, ecl, elj); else SNB_TILE_PACKED(false, false, p.ewPolyE, ecl, elj); }      // forces only (also: energy steps, slice not wanted)
 #undef SNB_TILE_PACKED
         // rotate-then-subtract leaves lane c holding slot (c+1)&7: one more rotation brings every slot home, then the two
         // partial sums of a slot (lanes c and c+8) are merged
@@ -663,13 +711,24 @@ __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<floa
     ux += __shfl_xor(ux, 16, 64); uy += __shfl_xor(uy, 16, 64); uz += __shfl_xor(uz, 16, 64);
     ox += __shfl_xor(ox, 32, 64); oy += __shfl_xor(oy, 32, 64); oz += __shfl_xor(oz, 32, 64);
     ux += __shfl_xor(ux, 32, 64); uy += __shfl_xor(uy, 32, 64); uz += __shfl_xor(uz, 32, 64);
-    if (row == 0) { fAddT<FIXED>(p, p.fx, (I * 32 + c), ox); fAddT<FIXED>(p, p.fy, (I * 32 + c), oy); fAddT<FIXED>(p, p.fz, (I * 32 + c), oz); }
-    if (row == 1) { fAddT<FIXED>(p, p.fx, (I * 32 + 16 + c), ux); fAddT<FIXED>(p, p.fy, (I * 32 + 16 + c), uy); fAddT<FIXED>(p, p.fz, (I * 32 + 16 + c), uz); }
-    if (ENERGY) { if (curNeeded) flushEnergy(); curSlice = -1; curNeeded = false; }
+    int Iout = I;
+    if constexpr (TILES) asm volatile("" : "+s"(Iout));      // (the i-atoms' 64-bit index is formed here, not held in two registers across the item's tiles)
+    if (row == 0) { fAddT<FIXED>(p, p.fx, (Iout * 32 + c), ox); fAddT<FIXED>(p, p.fy, (Iout * 32 + c), oy); fAddT<FIXED>(p, p.fz, (Iout * 32 + c), oz); }
+    if (row == 1) { fAddT<FIXED>(p, p.fx, (Iout * 32 + 16 + c), ux); fAddT<FIXED>(p, p.fy, (Iout * 32 + 16 + c), uy); fAddT<FIXED>(p, p.fz, (Iout * 32 + 16 + c), uz); }
+    if (RUNS) { if (curNeeded) flushEnergy(); curSlice = -1; curNeeded = false; }
     __builtin_amdgcn_wave_barrier();
     item = dyn ? wc.resolve(claimed) : item + nTileBlocks * 4;
     }   // work-item loop
     if (p.stepTrace && threadIdx.x == 0) p.stepTrace[p.traceSlot + 1] = (long long)wall_clock64();      // (plain store: the last work-group to leave writes last)
+}
+template <int MC, bool POLY, bool ENERGY, bool SWITCH, bool FIXED>
+__global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
+    directPackedBody<MC, POLY, ENERGY ? E_RUNS : E_NONE, SWITCH, FIXED>(p, q, nExclBlocks, nListBlocks);
+}
+// derivative steps (include_energy == 2): the same launch with the per-tile bookkeeping (no switching function: directKernel)
+template <int MC, bool POLY, bool FIXED>
+__global__ __launch_bounds__(256, 4) void k_directPackedSelected(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
+    directPackedBody<MC, POLY, E_TILES, false, FIXED>(p, q, nExclBlocks, nListBlocks);
 }
 
 // ---- energy-only tile kernels (steps with include_forces == 0) ------------------------------------
@@ -824,8 +883,8 @@ __global__ __launch_bounds__(256, 4) void k_directPackedEnergy(const DirectParam
             __builtin_amdgcn_wave_barrier();
             v2f fix = {0.f, 0.f}, fiy = {0.f, 0.f}, fiz = {0.f, 0.f};      // (not touched: FORCES == false)
             float fjx = 0.f, fjy = 0.f, fjz = 0.f;
-            if (maskIdx >= 0) tileStepsPacked<MC, true, POLY, true, SWITCH, false>(p, rdPos, rdSe, pix, piy, piz, sigi, qi, epsi, qi, epsi, c6i, lamL, maskA, maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj);
-            else tileStepsPacked<MC, false, POLY, true, SWITCH, false>(p, rdPos, rdSe, pix, piy, piz, sigi, qi, epsi, qi, epsi, c6i, lamL, maskA, maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj);
+            if (maskIdx >= 0) tileStepsPacked<MC, true, POLY, true, SWITCH, false>(p, p.ewPolyE, rdPos, rdSe, pix, piy, piz, sigi, qi, epsi, qi, epsi, c6i, lamL, maskA, maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj);
+            else tileStepsPacked<MC, false, POLY, true, SWITCH, false>(p, p.ewPolyE, rdPos, rdSe, pix, piy, piz, sigi, qi, epsi, qi, epsi, c6i, lamL, maskA, maskB, c, fix, fiy, fiz, fjx, fjy, fjz, ecl, elj);
             __builtin_amdgcn_wave_barrier();
         }
         if (curNeeded) flushEnergy();
@@ -839,7 +898,8 @@ __global__ __launch_bounds__(256, 4) void k_directPackedEnergy(const DirectParam
                                                  else hipLaunchKernelGGL(KERNEL, GRID, block, LDS, s, __VA_ARGS__); } while (0)
 template <typename Real> using TileKernel = void (*)(DirectParams<Real>, PairListParams<Real>, int, int);
 // The tile kernel of a forces step.  *packed: the single-precision packed kernel, which carries the pair lists whatever SNB_NO_FUSED_LISTS says.
-template <typename Real, int MC> static TileKernel<Real> directKernel(const DirectParams<Real>& p, bool wrap, bool energy, bool* packed) {
+template <typename Real, int MC> static TileKernel<Real> directKernel(const DirectParams<Real>& p, bool wrap, int energyMode, bool* packed) {
+    const bool energy = energyMode != E_NONE;      // (E_TILES: the packed kernel alone has the per-tile form; the scalar kernel keeps its runs)
     *packed = false;
     if constexpr (std::is_same<Real, float>::value) {
         if (!wrap && !(energy && switches().scalarEnergyKernel) && !(p.useSwitch && MC == MC_NOCUTOFF)) {
@@ -848,6 +908,16 @@ template <typename Real, int MC> static TileKernel<Real> directKernel(const Dire
             const int polyNeed = energy ? (SNB_POLY_FORCE | SNB_POLY_ENERGY) : SNB_POLY_FORCE;
             const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && (p.ewUsePoly & polyNeed) == polyNeed;
 #define SNB_PACKED(P, E, S) return p.fixed ? k_directPacked<MC, P, E, S, true> : k_directPacked<MC, P, E, S, false>
+            // derivative steps: the per-tile form where it is free of scratch -- not with the switching function and not under LJPME, whose energy
+            // bodies spill in either form (tests/test_host_cpu.py keeps the list of kernels that may); those keep the run-based kernel
+#define SNB_SELECTED(P) return p.fixed ? k_directPackedSelected<MC, P, true> : k_directPackedSelected<MC, P, false>
+            if constexpr (MC != MC_LJPME) {
+                if (energyMode == E_TILES && !p.useSwitch) {
+                    if constexpr (MC == MC_NOCUTOFF) SNB_SELECTED(false);
+                    else { if (poly) SNB_SELECTED(true); else SNB_SELECTED(false); }
+                }
+            }
+#undef SNB_SELECTED
             if constexpr (MC == MC_NOCUTOFF) { if (energy) SNB_PACKED(false, true, false); else SNB_PACKED(false, false, false); }
             else if (p.useSwitch && MC != MC_LJPME) {      // (no switching function under LJPME, Q2)
                 if (energy) { if (poly) SNB_PACKED(true, true, true); else SNB_PACKED(false, true, true); }
@@ -871,7 +941,7 @@ template <typename Real, int MC> static TileKernel<Real> directKernel(const Dire
     if (wrap) return energy ? k_direct<Real, MC, true, true, false> : k_direct<Real, MC, true, false, false>;
     return energy ? k_direct<Real, MC, false, true, false> : k_direct<Real, MC, false, false, false>;
 }
-template <typename Real, int MC> static bool launchDirectMC(const DirectParams<Real>& p, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
+template <typename Real, int MC> static bool launchDirectMC(const DirectParams<Real>& p, bool wrap, int energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
     const int myItems = p.numWork;
     if (myItems <= 0) return false;
     int nwg = (myItems + 3) / 4;
@@ -884,14 +954,14 @@ template <typename Real, int MC> static bool launchDirectMC(const DirectParams<R
     int nExclBlocks = 0, nListBlocks = 0;
     const bool fuseLists = lists != nullptr && (packed || !switches().noFusedLists);
     if (fuseLists) { q = *lists; nExclBlocks = (q.nExclAtoms + 255) / 256; nListBlocks = nExclBlocks + (q.n + 255) / 256; }
-    const size_t listLds = (fuseLists && energy) ? sizeof(double) * 2 * q.nSlices : 0;      // the energy list bodies reduce per slice in LDS
+    const size_t listLds = (fuseLists && energy != E_NONE) ? sizeof(double) * 2 * q.nSlices : 0;      // the energy list bodies reduce per slice in LDS
     const dim3 gridAll(nwg + nListBlocks), block(256);
     SNB_LAUNCH_LDS(kernel, gridAll, listLds, p, q, nExclBlocks, nListBlocks);
     return fuseLists;
 }
 // register allocation, in the hardware's units of 8 VGPRs (accumulation registers included), of the tile kernel launchDirect runs for
-// these arguments (of p: useSwitch, ewUsePoly, fixed); 16 when the runtime cannot tell
-template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int mc, bool wrap, bool energy) {
+// these arguments (of p: useSwitch, ewUsePoly, fixed; energy: 0 / 1 / 2 as include_energy); 16 when the runtime cannot tell
+template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int mc, bool wrap, int energy) {
     bool packed;
     TileKernel<Real> kernel;
     switch (mc) {
@@ -903,12 +973,12 @@ template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int mc
     hipFuncAttributes attr;
     return (hipFuncGetAttributes(&attr, (const void*)kernel) == hipSuccess && attr.numRegs > 0) ? (attr.numRegs + 7) / 8 : 16;
 }
-template int directVgprUnits<float>(const DirectParams<float>&, int, bool, bool);
-template int directVgprUnits<double>(const DirectParams<double>&, int, bool, bool);
+template int directVgprUnits<float>(const DirectParams<float>&, int, bool, int);
+template int directVgprUnits<double>(const DirectParams<double>&, int, bool, int);
 
 // Returns true when the launch also ran the pair lists passed in `lists` (single-precision forces-only tile kernel); otherwise the
 // caller launches them itself.
-template <typename Real> bool launchDirect(const DirectParams<Real>& p0, int mc, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
+template <typename Real> bool launchDirect(const DirectParams<Real>& p0, int mc, bool wrap, int energy, const PairListParams<Real>* lists, hipStream_t s, hipEvent_t evStart, hipEvent_t evStop, bool* timed) {
     const DirectParams<Real>& p = p0;
     switch (mc) {
         case MC_NOCUTOFF: return launchDirectMC<Real, MC_NOCUTOFF>(p, wrap, energy, lists, s, evStart, evStop, timed);
@@ -917,8 +987,8 @@ template <typename Real> bool launchDirect(const DirectParams<Real>& p0, int mc,
         default: return launchDirectMC<Real, MC_LJPME>(p, wrap, energy, lists, s, evStart, evStop, timed);
     }
 }
-template bool launchDirect<float>(const DirectParams<float>&, int, bool, bool, const PairListParams<float>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
-template bool launchDirect<double>(const DirectParams<double>&, int, bool, bool, const PairListParams<double>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
+template bool launchDirect<float>(const DirectParams<float>&, int, bool, int, const PairListParams<float>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
+template bool launchDirect<double>(const DirectParams<double>&, int, bool, int, const PairListParams<double>*, hipStream_t, hipEvent_t, hipEvent_t, bool*);
 
 // Energy-only step (include_forces == 0): k_directPackedEnergy wherever the forces step runs k_directPacked, k_directEnergy elsewhere (double
 // precision, per-pair wrapping; the guard on a NoCutoff switch only mirrors launchDirectMC -- the engine never sets useSwitch for NoCutoff).

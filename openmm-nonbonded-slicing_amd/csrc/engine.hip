@@ -266,7 +266,7 @@ public:
     // device counter, so the split follows the chain's actual duration.  Eager (stamped) steps stay serial: the per-kernel timers keep
     // measuring every kernel alone.  dOverlap: [0] the counter, [16 ...] the SNB_CU_SLOTS residency counts; zeroed by the gather pass.
     int numCUs = 256; DevBuf<int> dOverlap, dOverlapTrace; int overlapDumps = 3;
-    int pairVgprUnits[2][2];      // [per-pair wrapping][energy]: register allocation of the tile kernel a CU-limited launch runs (direct.hip directVgprUnits), resolved by the constructor
+    int pairVgprUnits[2][3];      // [per-pair wrapping][StepEnergy]: register allocation of the tile kernel a CU-limited launch runs (direct.hip directVgprUnits), resolved by the constructor
     struct EvSet { hipEvent_t e[5]; bool pending = false; KernelStamps ks; };   // start, direct0, direct1(=recip0 after pair lists), recip1, end; per-kernel stamps (snb_stats.sum_kernel_ms)
     std::vector<EvSet> ring; int ringPos = 0;
     // host-side definition
@@ -496,7 +496,7 @@ public:
             DirectParams<Real> p;
             std::memset(&p, 0, sizeof(p));
             p.useSwitch = useSwitch() ? 1 : 0; p.ewUsePoly = polyMask; p.fixed = fixedForces();
-            for (int w = 0; w < 2; w++) for (int e = 0; e < 2; e++) pairVgprUnits[w][e] = directVgprUnits<Real>(p, methodClass(), w != 0, e != 0);
+            for (int w = 0; w < 2; w++) for (int e = 0; e < 3; e++) pairVgprUnits[w][e] = directVgprUnits<Real>(p, methodClass(), w != 0, e);
         }
         if (sw.overlap) { dOverlap.resize(SNB_OVERLAP_INTS); HIPCHECK(hipMemsetAsync(dOverlap.p, 0, sizeof(int) * SNB_OVERLAP_INTS, stream)); }
         if (sw.stepTrace) { dStepTrace.resize(16); HIPCHECK(hipMemsetAsync(dStepTrace.p, 0, sizeof(long long) * 16, stream)); }
@@ -1814,10 +1814,10 @@ public:
                 p.gridCap = sw.overlapGridA > 0 ? sw.overlapGridA : 6 * numCUs; p.listsLast = 1;
                 p.cuTrace = dOverlapTrace.p;      // (SNB_OVERLAP_DEBUG; null otherwise)
                 directB = p; directMc = mc;
-                if (!sw.overlapByCount && p.cuLimit > 0) p.cuBaseMax = (p.cuLimit - 1) * pairVgprUnits[wrapMode][energy];      // its resident work-groups sit below (cuLimit - 1) allocations of this kernel
+                if (!sw.overlapByCount && p.cuLimit > 0) p.cuBaseMax = (p.cuLimit - 1) * pairVgprUnits[wrapMode][(int)r.energy];      // its resident work-groups sit below (cuLimit - 1) allocations of this kernel
             }
             if (!forces) { if (launchDirectEnergy<Real>(p, mc, wrapMode, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true; }
-            else if (launchDirect<Real>(p, mc, wrapMode, energy, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true;
+            else if (launchDirect<Real>(p, mc, wrapMode, (int)r.energy, (haveLists && !noFuse) ? &q : nullptr, stream, ev ? ev->e[1] : nullptr, ev ? ev->e[2] : nullptr, &kernelTimed)) listsDone = true;
         }
         if (ev && !kernelTimed) { HIPCHECK(hipEventRecord(ev->e[1], stream)); HIPCHECK(hipEventRecord(ev->e[2], stream)); }   // no tile kernel this step
         if (!listsDone) { if (forces) launchPairLists<Real>(q, energy, stream); else launchPairListsEnergy<Real>(q, stream); }
@@ -1847,7 +1847,7 @@ public:
                     if (!overlap) return;
                     directB.cuSlots = nullptr; directB.cuLimit = 0; directB.listsLast = 0; directB.traceSlot = 4; directB.gridCap = sw.overlapGridB > 0 ? sw.overlapGridB : 4 * numCUs;
                     bool t = false;
-                    launchDirect<Real>(directB, directMc, wrapMode, energy, nullptr, stream2, nullptr, nullptr, &t);
+                    launchDirect<Real>(directB, directMc, wrapMode, (int)r.energy, nullptr, stream2, nullptr, nullptr, &t);
                     HIPCHECK(hipStreamWaitEvent(stream2, evPairA, 0));
                 };
                 // (energy-only steps: each mesh ends with its slice-energy Gram sums -- no mix, no inverse transforms, no interpolation)

@@ -316,9 +316,10 @@ void launchZeroFill(void* ptr, size_t bytes, hipStream_t s);      // misc.hip: z
 void launchNeighborPublish(const int* counters, int* hostMapped, int seq, hipStream_t s);   // counters[0..7] + sequence number into mapped host memory (the host spins on it)
 
 // ---- launchers implemented in the .hip translation units -------------------------------------
-template <typename Real> bool launchDirect(const DirectParams<Real>& p, int methodClass, bool wrap, bool energy, const PairListParams<Real>* lists, hipStream_t s,
+// (energy: 0 = forces only, 1 = every slice's energies, 2 = the slices of p.sliceNeed alone, a derivative step -- as include_energy)
+template <typename Real> bool launchDirect(const DirectParams<Real>& p, int methodClass, bool wrap, int energy, const PairListParams<Real>* lists, hipStream_t s,
                                           hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr, bool* timed = nullptr);   // true: lists ran inside the launch
-template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int methodClass, bool wrap, bool energy);   // of the tile kernel launchDirect runs, in units of 8 registers
+template <typename Real> int directVgprUnits(const DirectParams<Real>& p, int methodClass, bool wrap, int energy);   // of the tile kernel launchDirect runs, in units of 8 registers
 template <typename Real> void launchPairLists(const PairListParams<Real>& p, bool energy, hipStream_t s);
 // include_forces == 0 steps: the slice energies of the tile kernel's tiles / of the two pair lists, no force arithmetic, no force stores
 template <typename Real> bool launchDirectEnergy(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, hipStream_t s,
