@@ -1123,13 +1123,14 @@ template <typename Real, bool ENERGY, bool FORCES> __device__ __forceinline__ vo
                 if (p.ljpme) {
                     const auto sej = p.sigeps[b];
                     const Real c6 = c6i * (Real(8) * sej.x * sej.x * sej.x * sej.y);
-                    const Real dar2 = p.alphaD * p.alphaD * r2, dar4 = dar2 * dar2, dar6 = dar4 * dar2;
+                    const Real dar2 = p.alphaD * p.alphaD * r2;
                     const Real invR2 = invR * invR;
-                    const Real expd = fexp(-dar2);
                     const Real coef = c6 * invR2 * invR2 * invR2;
-                    if (wantE) __hip_atomic_fetch_add(&s_sliceE[2 * slice + 1], 0.5 * (double)(coef * (Real(1) - expd * (Real(1) + dar2 + Real(0.5) * dar4))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    Real h3, h4;      // 1 - exp(-dar2) (1 + dar2 + dar2^2/2 [+ dar2^3/6]), by series where they cancel (pair_math.h)
+                    dispersionExclusion(dar2, fexp(-dar2), h3, h4);
+                    if (wantE) __hip_atomic_fetch_add(&s_sliceE[2 * slice + 1], 0.5 * (double)(coef * h3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     // reference: dEdR = -6 c6 r^-8 (...), forces[ii] -= lam*dEdR*delta  =>  +6 lam c6 r^-8 (...) * delta on ii
-                    f += lamL * Real(6) * coef * invR2 * (Real(1) - expd * (Real(1) + dar2 + Real(0.5) * dar4 + dar6 * Real(1.0 / 6.0)));
+                    f += lamL * Real(6) * coef * invR2 * h4;
                 }
                 fx += f * dx; fy += f * dy; fz += f * dz;
             }

@@ -79,9 +79,11 @@ struct PairEnergy {
             const auto sej = p.sigeps[b];
             const Real c6i = Real(8) * sei.x * sei.x * sei.x * sei.y;
             const Real c6 = c6i * (Real(8) * sej.x * sej.x * sej.x * sej.y);
-            const Real dar2 = p.alphaD * p.alphaD * r2, dar4 = dar2 * dar2;
+            const Real dar2 = p.alphaD * p.alphaD * r2;
             const Real invR2 = invR * invR;
-            v[1] = (double)(c6 * invR2 * invR2 * invR2 * (Real(1) - fexp(-dar2) * (Real(1) + dar2 + Real(0.5) * dar4)));
+            Real h3, h4;
+            dispersionExclusion(dar2, fexp(-dar2), h3, h4);
+            v[1] = (double)(c6 * invR2 * invR2 * invR2 * h3);
         }
     }
 };

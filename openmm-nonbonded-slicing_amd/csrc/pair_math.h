@@ -41,6 +41,29 @@ __device__ inline float exclusionG(float x, float e, double erfv) {
     return (float)erfv - x * e * 1.1283791670955126f;
 }
 __device__ inline double exclusionG(double x, double e, double erfv) { return erfv - x * e * 1.1283791670955126; }
+// The LJPME part of the exclusion correction: the radial factors  h3(y) = 1 - e (1 + y + y^2/2)  of the energy and  h4(y) = h3(y) - e y^3/6
+// of the force, y = (alpha_d r)^2, e = exp(-y).  They cancel to y^3/6 and y^4/24: in float the rounding of the bracket (1e-7 absolute) is
+// divided by y^4/24, 8 % of the force factor at alpha_d r = 0.25 and all of it at 0.125.  Below y = 1 the identity
+// 1 = e exp(y) gives  h4 = e sum_{k >= 4} y^k / k!  with every term positive, here to k = 13 (truncation 24 y^10 / 14! < 3e-10 relative),
+// and h3 = h4 + e y^3/6; double keeps the closed form on libm's exp.
+__device__ inline void dispersionExclusion(float y, float e, float& h3, float& h4) {
+    const float y2 = y * y, y3 = y2 * y;
+    if (y < 1.0f) {
+        float p = 1.0f + y * (1.0f / 13);
+#pragma unroll
+        for (int k = 12; k >= 5; k--) p = 1.0f + y * (1.0f / k) * p;
+        h4 = e * (y2 * y2 * (1.0f / 24)) * p;
+        h3 = h4 + e * (y3 * (1.0f / 6));
+        return;
+    }
+    h3 = 1.0f - e * (1.0f + y + 0.5f * y2);
+    h4 = 1.0f - e * (1.0f + y + 0.5f * y2 + y3 * (1.0f / 6));
+}
+__device__ inline void dispersionExclusion(double y, double e, double& h3, double& h4) {
+    const double y2 = y * y;
+    h3 = 1.0 - e * (1.0 + y + 0.5 * y2);
+    h4 = 1.0 - e * (1.0 + y + 0.5 * y2 + y2 * y * (1.0 / 6.0));
+}
 
 __device__ inline void ldsAdd(float* p, float v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ inline void ldsAdd(double* p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
