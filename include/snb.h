@@ -59,7 +59,12 @@ typedef enum { SNB_SINGLE = 0, SNB_DOUBLE = 1, SNB_MIXED = 2 } snb_precision;
 typedef struct {
     int32_t abi_version;        /* SNB_ABI_VERSION                                                      */
     int32_t n_atoms;
-    int32_t n_subsets;
+    int32_t n_subsets;          /* >= 1.  snb_create returns SNB_ERR_UNSUPPORTED (snb_last_error names the numbers) for counts whose kernels cannot
+                                 * get their LDS: more than 77 subsets with any method (the pair-list energy kernels reduce n(n+1)/2 slices in 16 bytes
+                                 * each, at most 48 KB), and with PME / LJPME when one x line of a mesh for every subset this engine holds
+                                 * (n_subsets, or its share when sharded) exceeds the device's LDS: 2 nx n sizeof(complex) + nx sizeof(real) +
+                                 * nx sizeof(complex) bytes, complex = 2 reals of 4 (single, mixed) or 8 (double) bytes -- on 160 KB in double
+                                 * precision that is 42 subsets on a 120 mesh, 28 on a 180 mesh.  Tested up to 20 subsets. */
     int32_t method;             /* snb_method                                                           */
     int32_t precision;          /* snb_precision: arithmetic type of every kernel                       */
     int32_t use_switch;         /* LJ switching function (ignored for NoCutoff and LJPME, Quirk Q2)     */

@@ -10,6 +10,7 @@
 #include "switches.h"
 #include "host_lists.h"
 #include "ewald_fit.h"
+#include "pme_sizes.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -481,6 +482,8 @@ public:
     void dropGraph() { for (auto& g : graphs) g.stale = true; }
     void destroyGraphs() { for (auto& g : graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec); graphs.clear(); graphVictim = 0; }
     bool lastRecip = false;
+    std::vector<int> hostGridSubset;      // subset of each held mesh
+    unsigned long long emptyGrids = 0;    // PmeParams::emptyGrids, from the subsets of snb_set_particles (a change of subsets rebuilds)
     snb_stats stats;
 
     Engine(const snb_config& c) {
@@ -532,6 +535,7 @@ public:
             std::vector<int> gs = cfg.shard_count == 1 ? std::vector<int>() : ownedSubsets;
             if (cfg.shard_count == 1) { gs.resize(nsub); std::iota(gs.begin(), gs.end(), 0); }
             gridSubset.upload(gs, stream);
+            hostGridSubset = gs;
         }
     }
     ~Engine() override {
@@ -599,6 +603,13 @@ public:
             if (subset[i] != sub[i]) subsetsChanged = true;      // subsets decide the sorted order and the block layout
         }
         charge.assign(q, q + N); sigma.assign(sg, sg + N); epsilon.assign(ep, ep + N); subset.assign(sub, sub + N);
+        {      // meshes of subsets without atoms: exactly zero in exact arithmetic, but the plane path's inverse z pass transforms two meshes as one
+               // complex line and leaves the partner's rounding in them -- a sharded rank, which reads every mesh it holds, skips them
+            std::vector<int> count(nsub, 0);
+            for (int i = 0; i < N; i++) count[sub[i]]++;
+            emptyGrids = 0;
+            for (size_t g = 0; g < hostGridSubset.size() && g < 64; g++) if (count[hostGridSubset[g]] == 0) emptyGrids |= 1ull << g;
+        }
         basePDirty = true;
         haveParticles = true;
         // new charges / sigmas / epsilons alone (parameter offsets, updateParametersInContext) do not touch the neighbour structure:
@@ -1214,7 +1225,7 @@ public:
                              (box[3] * box[7] - box[4] * box[6]) * sc, -box[0] * box[7] * sc, box[0] * box[4] * sc};
         for (int i = 0; i < 9; i++) { p.recip[i] = (Real)r[i]; p.recipLo[i] = (Real)(r[i] - (double)p.recip[i]); }
         p.alpha = (Real)plan.alpha; p.volume = (Real)det; p.dispersion = plan.dispersion ? 1 : 0;
-        p.lambdas = dLambdas.p; p.sliceNeed = need; p.gridSubset = gridSubset.p; p.nsubTotal = nsub; p.mix = cfg.shard_count == 1 ? 1 : 0;
+        p.lambdas = dLambdas.p; p.sliceNeed = need; p.gridSubset = gridSubset.p; p.emptyGrids = emptyGrids; p.nsubTotal = nsub; p.mix = cfg.shard_count == 1 ? 1 : 0;
         p.mix16 = sw.mix16 ? 1 : 0;
         p.sliceE = sliceE.p; p.fpx = fpx.p; p.fpy = fpy.p; p.fpz = fpz.p; p.wantEnergy = wantEnergy ? 1 : 0;
         // brick kernels: the sort columns were cut for the Coulomb mesh; any mesh whose cells tile those columns can use them,
@@ -2330,6 +2341,32 @@ snb_status snb_create(const snb_config* cfg, snb_handle* out) {
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_createError = "hip: no HIP device available (the engine has no CPU fallback)"; return SNB_ERR_HIP; }
         if (cfg->device < 0 || cfg->device >= ndev) { g_createError = "invalid device ordinal"; return SNB_ERR_INVALID_ARGUMENT; }
         DeviceScope scope(cfg->device);
+        {      // LDS requests that grow with the subset count (pme_sizes.h): what cannot run is refused here, not skipped at the launch
+            char msg[320];
+            const long long nSlices = (long long)cfg->n_subsets * (cfg->n_subsets + 1) / 2;
+            if (!pairListLdsFits(nSlices)) {
+                snprintf(msg, sizeof(msg), "n_subsets = %d: the pair-list energy kernels reduce %lld slices in %zu bytes of LDS, more than the %zu they may request",
+                         (int)cfg->n_subsets, nSlices, pairListLds(nSlices), kPairListLdsMax);
+                g_createError = msg; return SNB_ERR_UNSUPPORTED;
+            }
+            if (cfg->method == SNB_PME || cfg->method == SNB_LJPME) {
+                hipDeviceProp_t prop;
+                if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) { g_createError = "hip: hipGetDeviceProperties failed"; return SNB_ERR_HIP; }
+                // (a work-group may raise its limit to all the LDS of a compute unit: hipFuncAttributeMaxDynamicSharedMemorySize)
+                const size_t limit = std::max((size_t)prop.sharedMemPerBlock, (size_t)prop.maxSharedMemoryPerMultiProcessor);
+                const int shards = cfg->shard_count > 1 ? cfg->shard_count : 1;
+                const int nGrids = (cfg->n_subsets - (shards > 1 ? cfg->shard_rank : 0) + shards - 1) / shards;      // the meshes this engine holds
+                const size_t realBytes = cfg->precision == SNB_DOUBLE ? 8 : 4;
+                for (int mesh = 0; mesh < (cfg->method == SNB_LJPME ? 2 : 1); mesh++) {
+                    const int nx = legalGridSize(mesh ? cfg->dgrid[0] : cfg->grid[0]);
+                    if (nGrids > 0 && !convLdsFits(nx, nGrids, realBytes, limit)) {
+                        snprintf(msg, sizeof(msg), "%s mesh with nx = %d and %d subsets in %s precision: the x kernel of the reciprocal sum needs %zu bytes of LDS at one column per work-group, the device has %zu",
+                                 mesh ? "dispersion" : "PME", nx, nGrids, realBytes == 8 ? "double" : "single", convLdsNeed(nx, nGrids, realBytes), limit);
+                        g_createError = msg; return SNB_ERR_UNSUPPORTED;
+                    }
+                }
+            }
+        }
         EngineBase* e = cfg->precision == SNB_DOUBLE ? (EngineBase*)new Engine<double>(*cfg) : (EngineBase*)new Engine<float>(*cfg);
         *out = new snb_engine{e};
         return SNB_OK;

@@ -17,6 +17,8 @@
 //  * the real axis (z) is transformed with the imaginary half implied, writing nz/2+1 complex outputs.
 #include "snb_internal.h"
 #include "switches.h"
+#include "pme_sizes.h"
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include <algorithm>
@@ -1142,6 +1144,7 @@ template <typename Real, int R1, int R2, int NT = 512, bool EONLY = false> __glo
     Cx<Real>* tw = B + (size_t)nx * BS;                                // [nx] roots of unity
     Real* et = reinterpret_cast<Real*>(tw + nx);                       // [nx][NB]
     __shared__ double s_red[(NT / 64) * 4];
+    static_assert(sizeof(s_red) <= kConvStaticLds, "pme_sizes.h: the guard of snb_create counts the static LDS of this kernel");
     const size_t strideK = (size_t)nCols;                              // ny*nzc
     const size_t strideSub = (size_t)nx * nCols;
     Cx<Real>* g = reinterpret_cast<Cx<Real>*>(p.gridCplx);
@@ -1926,15 +1929,18 @@ template <typename Real> void launchPmeForwardFFT(const PmeParams<Real>& p, hipS
 template <typename Real> void launchPmeConvolution(const PmeParams<Real>& p, hipStream_t s) {
     const int nx = p.d.nx;
     const int nCols = p.d.ny * p.d.nzc;
-    const size_t perCol = (size_t)2 * nx * p.nsub * sizeof(Cx<Real>) + (size_t)nx * sizeof(Real);
-    const size_t twBytes = (size_t)nx * sizeof(Cx<Real>);
-    // columns per work-group: 8 adjacent (ky,kz) columns are one 64-byte line per (subset, kx) row -- measured on c3 (4 subsets):
-    // NB = 4: 68 us, 5: 64, 7: 69, 8: 48.5, 16: 60.5 -- so 8 when that fits ~72 KB of LDS, else 4, 2, 1
-    const int ldsKB = switches().convLdsKB;
-    int NB = 8;
-    while (NB > 1 && perCol * NB > (size_t)ldsKB * 1024) NB >>= 1;
-    const size_t lds = perCol * NB + twBytes;
-    launchConvolveX<Real>(p.d.rx1, p.d.rx2, dim3((unsigned)((nCols + NB - 1) / NB)), lds, s, p, NB, nCols);
+    // columns per work-group and the LDS they take: pme_sizes.h (snb_create has refused an engine whose request at NB = 1 exceeds the device)
+    const ConvLds c = convLds(nx, p.nsub, sizeof(Real), switches().convLdsKB);
+    const int NB = c.NB;
+    if (switches().verbose) {      // once per mesh and shape: the tests read the columns per work-group the launch really uses
+        static int last[2][3] = {{0, 0, 0}, {0, 0, 0}};
+        int* l = last[p.dispersion ? 1 : 0];
+        if (l[0] != nx || l[1] != p.nsub || l[2] != NB) {
+            fprintf(stderr, "[snb] x kernel, %s mesh: nx %d, %d subsets, %d columns per work-group, %zu bytes of LDS\n", p.dispersion ? "dispersion" : "coulomb", nx, p.nsub, NB, c.total);
+            l[0] = nx; l[1] = p.nsub; l[2] = NB;
+        }
+    }
+    launchConvolveX<Real>(p.d.rx1, p.d.rx2, dim3((unsigned)((nCols + NB - 1) / NB)), c.total, s, p, NB, nCols);
 }
 
 template <typename Real> void launchPmeInverseFFT(const PmeParams<Real>& p, hipStream_t s) {
@@ -2002,6 +2008,7 @@ template <typename Real> __global__ __launch_bounds__(256) void k_interpolate(co
             if (p.mix) slot = p.atomGrid[gid];   // own subset's mixed grid
             else {
                 slot = gI;
+                if (gI < 64 && ((p.emptyGrids >> gI) & 1)) continue;      // the mesh of a subset without atoms
                 const int gj = p.gridSubset[gI];
                 const int slice = si > gj ? si * (si + 1) / 2 + gj : gj * (gj + 1) / 2 + si;
                 lam = p.lambdas[2 * slice + term];
@@ -2117,6 +2124,7 @@ template <typename Real, int NT, bool CTX> __global__ __launch_bounds__(NT) void
     const int g2 = p.groupX * p.groupY;
     for (int slot = 0; slot < p.nsub; slot++) {
         const int gj = p.gridSubset[slot];
+        if (!p.mix && slot < 64 && ((p.emptyGrids >> slot) & 1)) continue;      // sharded: the mesh of a subset without atoms (uniform)
         // unsharded (mix == 1): grid `slot` is the lambda-mixed potential felt by subset gj, so only that subset's atoms read it (and a
         // brick without such atoms is not even staged); sharded: every subset's atoms read every held grid, scaled by lambda
         const int vBegin = p.mix ? s_pref[gj * g2] : 0, vEnd = p.mix ? s_pref[(gj + 1) * g2] : total;

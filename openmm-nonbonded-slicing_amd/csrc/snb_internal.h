@@ -231,6 +231,7 @@ template <typename Real> struct PmeParams {
     const Real* lambdas;      // [S*2]
     const int* sliceNeed;     // [S] energy steps: slices whose reciprocal energy is wanted
     const int* gridSubset;    // [nsub] subset id of each held grid
+    unsigned long long emptyGrids;      // bit g: held grid g (< 64) belongs to a subset without atoms; a sharded rank's interpolation skips it
     int nsubTotal;
     int mix;                  // 1: lambda-mix the potentials in k-space (unsharded); 0: plain convolution (sharded)
     int mix16;                // test switch (SNB_MIX_16X16): the 16 x 16 x 4 matrix-core form of the mix also for <= 4 subsets
