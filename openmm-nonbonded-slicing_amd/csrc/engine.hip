@@ -211,25 +211,14 @@ template <typename Real> struct PmePlan {
     // own-atoms spreader (pme.hip k_spreadOwn / k_spreadMerge): geometry and buffers, sized at rebuild time
     int ownSlabs = 0, ownMargin = 1; DevBuf<unsigned char> ownPartial; DevBuf<int> ownBusy; DevBuf<int2> strays;
     void init(const int g[3], int nGrids, hipStream_t s) {
-        d.nx = g[0]; d.ny = g[1]; d.nz = g[2]; d.nzc = g[2] / 2 + 1;
-        if (!factorize(d.nx, d.fx, &d.nfx) || !factorize(d.ny, d.fy, &d.nfy) || !factorize(d.nz, d.fz, &d.nfz)) throw HipError{"PME mesh size is not FFT-legal"};
+        if (!planDims(g, sizeof(Real), switches(), d)) throw HipError{"PME mesh size is not FFT-legal"};      // sizes and splits: pme_plan.h
         // pme.hip divides index values by reciprocal multiplication (FastDiv: exact for dividends below 2^22).  Its dividends are LDS element
         // indices of one work-group (< 40 960), line / chunk counts of one brick, and indices into one mesh plane or one (y, kz) slab:
         // at most 1024 x 1024 = 2^20 under this cap.
         if (d.nx > 1024 || d.ny > 1024 || d.nz > 1024) throw HipError{"PME mesh dimensions above 1024 are not supported"};
-        splitTwoPass(d.nx, &d.rx1, &d.rx2); splitTwoPass(d.ny, &d.ry1, &d.ry2); splitTwoPass(d.nz, &d.rz1, &d.rz2);
-        splitPlane(d.nx, &d.px1, &d.px2); splitPlane(d.ny, &d.py1, &d.py2);
-        // measured on MI355X (120^3 = 8 x 15, 4 grids, single precision, Winograd radix-3/5 butterflies): two-pass register FFT vs
-        // staged Stockham: inverse z 18.2 vs 23.5 us, y 30.6 vs 32.4, fused x/convolution 68.6 vs 71.0.  SNB_FFT_TWOPASS=0/1 overrides.
-        // Round 3, double precision (c5, 180^3 = 12 x 15 and 90^3 = 9 x 10): the register passes win on the y and z axes (y 183 -> 150 us,
-        // inverse z 185 -> 134, 90^3: 32 -> 22 and 21 -> 14) and in the fused x kernel of the 90^3 mesh (63 -> 42), but the x kernel of the
-        // 180^3 mesh, which also holds the spectra of all subsets, spills with 15-point transforms in double (351 -> 488): staged there.
-        if (!switches().fftTwoPass) d.rx1 = d.ry1 = d.rz1 = d.rx2 = d.ry2 = d.rz2 = 0;
-        // (round 4: the fused x kernel runs 15- / 16-point transforms in double with 256 threads and 256 registers; SNB_CONVX_STAGED_F64=1 restores the staged form)
-        if (sizeof(Real) == 8 && std::max(d.rx1, d.rx2) > 12 && switches().convxStagedF64) d.rx1 = d.rx2 = 0;
         gridReal.resize((size_t)nGrids * d.nx * d.ny * d.nz);
         gridCplx.resize((size_t)nGrids * d.nx * d.ny * d.nzc);
-        if (sizeof(Real) == 4 && (size_t)d.nx * (d.ny | 1) * 8 <= 156 * 1024) { gridCplxB.resize((size_t)nGrids * d.nx * (d.ny + 8) * d.nzc);      // (plane path, planes that fit LDS; y padded to whole tiles of the inverse z kernel)
+        if (planePath(d, nGrids, sizeof(Real), switches()).buffers) { gridCplxB.resize((size_t)nGrids * d.nx * (d.ny + 8) * d.nzc);      // (plane path, planes that fit LDS; y padded to whole tiles of the inverse z kernel)
              planeEterm.resize((size_t)d.nx * d.ny * d.nzc); planeEtermReady = false; }
         auto tw = [&](int n, DevBuf<typename Vec<Real>::T2>& buf) {
             std::vector<typename Vec<Real>::T2> h(n);
@@ -1220,9 +1209,8 @@ public:
         p.fixDev = dFixScale.p ? dFixScale.p + (plan.dispersion ? 2 : 0) : nullptr;      // (k_fixScale keeps it in step with the parameters)
         p.gridReal = plan.gridReal.p; p.gridCplx = plan.gridCplx.p; p.planeB = plan.gridCplxB.p; p.planeEterm = plan.planeEtermReady ? plan.planeEterm.p : nullptr; p.twx = plan.twx.p; p.twy = plan.twy.p; p.twz = plan.twz.p;
         p.modx = plan.modx.p; p.mody = plan.mody.p; p.modz = plan.modz.p;
-        const double det = box[0] * box[4] * box[8], sc = 1.0 / det;
-        const double r[9] = {box[4] * box[8] * sc, 0, 0, -box[3] * box[8] * sc, box[0] * box[8] * sc, 0,
-                             (box[3] * box[7] - box[4] * box[6]) * sc, -box[0] * box[7] * sc, box[0] * box[4] * sc};
+        const double det = box[0] * box[4] * box[8];
+        double r[9]; recipBoxRows(box, r);
         for (int i = 0; i < 9; i++) { p.recip[i] = (Real)r[i]; p.recipLo[i] = (Real)(r[i] - (double)p.recip[i]); }
         p.alpha = (Real)plan.alpha; p.volume = (Real)det; p.dispersion = plan.dispersion ? 1 : 0;
         p.lambdas = dLambdas.p; p.sliceNeed = need; p.gridSubset = gridSubset.p; p.emptyGrids = emptyGrids; p.nsubTotal = nsub; p.mix = cfg.shard_count == 1 ? 1 : 0;
@@ -1235,28 +1223,16 @@ public:
         // measured on c3: f64 accumulation 1 slab 110 us, 2 slabs 105 us, 4 slabs 145 us; fixed-point (single precision, even nz) 1 slab 61 us, 2 slabs 67 us
         if (plan.d.nz % 2 == 0 && plan.d.nz >= 32 && !(sizeof(Real) == 4)) p.zSlabs = 2;
         if (sw.zSlabs >= 1 && plan.d.nz % sw.zSlabs == 0) p.zSlabs = sw.zSlabs;
-        int ncx, ncy, gx, gy;
-        if (brickGeometry(plan, ncx, ncy, gx, gy)) {
-            p.sortNcx = ncx; p.sortNcy = ncy; p.groupX = gx; p.groupY = gy; p.colRange = colRange.p;
+        const BrickGeometry b = bricksFor(plan);
+        if (b.ok) {
+            p.sortNcx = b.ncx; p.sortNcy = b.ncy; p.groupX = b.gx; p.groupY = b.gy; p.colRange = colRange.p;
             p.ownSlabs = plan.ownSlabs; p.ownMargin = plan.ownMargin; p.ownPartial = plan.ownPartial.p; p.ownBusy = plan.ownBusy.p;
             p.strays = plan.strays.p; p.strayCount = dStrayCount.p ? dStrayCount.p + (plan.dispersion ? 1 : 0) : nullptr;
             if (!p.ownPartial || !p.ownBusy || !p.strays || !p.strayCount) p.ownSlabs = 0;
         }
     }
-    // brick kernels: do this mesh's cells tile the sort columns (cut for the Coulomb mesh)?  Bricks of `group` columns when one column is
-    // narrower than 5 cells (stencil 4 + 1 cell of drift).
-    bool brickGeometry(const PmePlan<Real>& plan, int& ncx, int& ncy, int& gx, int& gy) const {
-        if (colCells[0] <= 0) return false;
-        ncx = pme.d.nx / colCells[0]; ncy = pme.d.ny / colCells[1];
-        const int gMin = sw.brickGroup;
-        auto group = [gMin](int n, int ncols) { if (n % ncols) return 0; const int cpc = n / ncols; for (int g = gMin; g <= 4; g++) if (g * cpc >= 5 && ncols % g == 0) return g; return 0; };
-        gx = group(plan.d.nx, ncx); gy = group(plan.d.ny, ncy);
-        const bool packable = plan.d.nx < 1024 && plan.d.ny < 1024 && plan.d.nz < 1024;   // k_pmeCells packs 10 bits per axis
-        return packable && gx > 0 && gy > 0 && sizeof(double) * (size_t)(gx * plan.d.nx / ncx) * (gy * plan.d.ny / ncy) * plan.d.nz <= 100 * 1024;
-    }
-    // Geometry and buffers of the own-atoms spreader for one mesh (called from rebuild(): nothing may allocate inside a graph capture).
-    // Margin: the cells an atom can drift across its column's border during a list's life (skin / 2), at least one; slabs: the fewest that
-    // bring a work-group's LDS region under 40 KB (four work-groups per CU), at least two.
+    // brick kernels: do this mesh's cells tile the sort columns (cut for the Coulomb mesh, `pme`)?  pme_plan.h
+    BrickGeometry bricksFor(const PmePlan<Real>& plan) const { return brickGeometry(plan.d, pme.d, colCells, sw.brickGroup); }
     // Plane path (pme.hip k_planeXY): its table of reciprocal-space kernel values follows the box and alpha, both fixed between rebuilds.
     void planPlaneTable(PmePlan<Real>& plan) {
         if (!plan.planeEterm.p || !plan.gridCplxB.p || nGrids <= 0) { plan.planeEtermReady = false; return; }
@@ -1271,53 +1247,34 @@ public:
         plan.planeEtermReady = true;
     }
     // SNB_VERBOSE: the spreader planned for a mesh at this rebuild.  Sort columns and bricks decide between the atomic spreader and the brick
-    // kernels for good; the own-atoms spreader is only planned here -- launchSpreadOwn (pme.hip) can still decline it at the launch, and
-    // that it ran shows only where the plane path follows it (no y-pass stamps in slots 3 / 5).
+    // kernels for good; of the own-atoms spreader the line states the planned slabs (pme_plan.h OwnSpread::slabs) -- the launch can still
+    // decline them (OwnSpread::runs), and that it ran shows only where the plane path follows it (no y-pass stamps in slots 3 / 5).
     void describeMesh(const char* name, const PmePlan<Real>& plan) const {
-        int ncx = 0, ncy = 0, gx = 0, gy = 0;
-        const bool bricks = nGrids > 0 && brickGeometry(plan, ncx, ncy, gx, gy);
+        const BrickGeometry b = bricksFor(plan);
+        const bool bricks = nGrids > 0 && b.ok;
         // (the sort columns are cut on the Coulomb mesh, `pme`, for every mesh; the mesh size and the bricks are this plan's)
         fprintf(stderr, "[snb] %s mesh %d x %d x %d: sort columns %d x %d of %d x %d cells, %s", name, plan.d.nx, plan.d.ny, plan.d.nz,
                 colCells[0] > 0 ? pme.d.nx / colCells[0] : 0, colCells[0] > 0 ? pme.d.ny / colCells[1] : 0, colCells[0], colCells[1],
                 !bricks ? "atomic spreader" : "");
-        if (bricks) fprintf(stderr, "bricks of %d x %d columns, %s (slabs %d, margin %d)", gx, gy, plan.ownSlabs > 0 ? "own-atoms spreader planned" : "scanning brick spreader", plan.ownSlabs, plan.ownMargin);
+        if (bricks) fprintf(stderr, "bricks of %d x %d columns, %s (slabs %d, margin %d)", b.gx, b.gy, plan.ownSlabs > 0 ? "own-atoms spreader planned" : "scanning brick spreader", plan.ownSlabs, plan.ownMargin);
         // the (R1, R2) instantiations the mesh size selects (0 * 0: the staged transforms; plane splits 0 * 0: no plane kernel for this size)
         const PmePlanDims& d = plan.d;
         fprintf(stderr, "; fft splits x %d*%d y %d*%d z %d*%d, plane splits x %d*%d y %d*%d (%s)\n", d.rx1, d.rx2, d.ry1, d.ry2, d.rz1, d.rz2, d.px1, d.px2, d.py1, d.py2,
                 (d.px1 <= 0 || d.py1 <= 0) ? "none" : planeIsStatic(d) ? "static" : "run-time");
     }
+    // Geometry and buffers of the own-atoms spreader for one mesh (called from rebuild(): nothing may allocate inside a graph capture).
+    // Margin and slabs: pme_plan.h ownSpreadMargin / ownSpread; launchSpreadOwn (pme.hip) calls the same function with the same inputs.
     void planOwnSpread(PmePlan<Real>& plan) {
         plan.ownSlabs = 0;
-        int ncx, ncy, gx, gy;
-        if (nGrids <= 0 || !brickGeometry(plan, ncx, ncy, gx, gy)) return;
-        const double det = box[0] * box[4] * box[8], sc = 1.0 / det;
-        const double r[9] = {box[4] * box[8] * sc, 0, 0, -box[3] * box[8] * sc, box[0] * box[8] * sc, 0,
-                             (box[3] * box[7] - box[4] * box[6]) * sc, -box[0] * box[7] * sc, box[0] * box[4] * sc};
-        const double perNmX = plan.d.nx * std::sqrt(r[0] * r[0] + r[3] * r[3] + r[6] * r[6]), perNmY = plan.d.ny * std::sqrt(r[1] * r[1] + r[4] * r[4] + r[7] * r[7]);      // mesh cells per nm of displacement
-        int M = std::max(1, (int)std::ceil(0.5 * std::max(cfg.neighbor_padding, 0.0) * std::max(perNmX, perNmY) + 0.01));
-        if (sw.spreadMargin >= 0) M = sw.spreadMargin;
-        const bool fixed = sizeof(Real) == 4 && !sw.noFixedSpread;
-        const size_t accBytes = fixed ? 4 : 8;
-        const int cx = gx * (plan.d.nx / ncx), cy = gy * (plan.d.ny / ncy), nz = plan.d.nz;
-        const int RX = cx + 4 + 2 * M, RY = cy + 4 + 2 * M;
-        if (RX > plan.d.nx || RY > plan.d.ny || gx * gy > 16 || nz > 256) return;      // (nz > 256 ends here: launchSpreadOwn's own test of it is never reached)
-        int best = 0;
-        const int forced = sw.ownSlabs;
-        for (int pass = 0; pass < 2 && !best; pass++)
-            for (int k = 2; k <= 32; k++) {      // (at least two: a single slab's region, nz + 4 planes, would wrap onto itself)
-                if (forced > 0 && k != forced) continue;
-                if (nz % k) continue;
-                const int sz = nz / k;
-                if (sz < 4 || (sz & 1)) continue;      // (8- or 16-byte copies of the regions)
-                if (accBytes * (size_t)RX * RY * (sz + 4) <= (size_t)(pass == 0 ? 40 : 64) * 1024) { best = k; break; }
-            }
-        if (!best) return;
-        // few, wide bricks (coarse mesh, 2 x 2 columns per brick): more slabs until a grid has ~400 work-groups (c3l's 60^3 dispersion mesh: 100 bricks)
-        if (forced <= 0) for (int k = best + 1; k <= 16 && (ncx / gx) * (ncy / gy) * best < 400; k++) if (nz % k == 0 && (nz / k) >= 8 && !((nz / k) & 1)) best = k;
-        const size_t nreg = (size_t)nGrids * (ncx / gx) * (ncy / gy) * best;
-        plan.ownPartial.resize(nreg * RX * RY * (nz / best + 4) * accBytes);
-        plan.ownBusy.resize(nreg); plan.strays.resize(std::max(Npad, 1));
-        plan.ownSlabs = best; plan.ownMargin = M;
+        const BrickGeometry b = bricksFor(plan);
+        if (nGrids <= 0 || !b.ok) return;
+        double r[9]; recipBoxRows(box, r);
+        const int M = ownSpreadMargin(plan.d, r, cfg.neighbor_padding, sw);
+        const OwnSpread o = ownSpread(plan.d, b, nGrids, sizeof(Real), M, sw);
+        if (!o.slabs) return;
+        plan.ownPartial.resize(o.partialBytes);
+        plan.ownBusy.resize(o.regions); plan.strays.resize(std::max(Npad, 1));
+        plan.ownSlabs = o.slabs; plan.ownMargin = M;
     }
 
     // What every evaluation starts with: the state checks, then the neighbour-list rules -- a due rebuild happens (in line, or as the exchange of a

@@ -18,6 +18,7 @@
 #include "snb_internal.h"
 #include "switches.h"
 #include "pme_sizes.h"
+#include "pme_plan.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -28,6 +29,31 @@ namespace snb {
 
 thread_local KernelStamps* g_stamps = nullptr;
 template <typename Real> static inline int stampSlot(const PmeParams<Real>& p, int k) { return k + (p.dispersion ? 8 : 0); }
+
+// Every launch that asks for dynamic LDS goes through here: raise the kernel's limit to the request, then launch (stamped when the step is
+// timed and a slot >= 0 is offered).  The same kernel pointer serves both calls.
+template <typename... KArgs, typename... Args>
+static void launchLds(int slot, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    SNB_STAMPED_LAUNCH(slot, kernel, grid, block, lds, s, static_cast<KArgs>(args)...);
+}
+// Run-time (r1, r2) -> the compile-time constants of an instantiated pair of pme_plan.h's lists: f(integral_constant A, B); <0, 0> (the
+// staged / run-time forms) for everything else.
+template <int A, int B, typename F> static void callPair(F& f) { f(std::integral_constant<int, A>{}, std::integral_constant<int, B>{}); }
+template <typename F> static void forFftPair(int r1, int r2, F f) {
+#define X(A, B) if (r1 == A && r2 == B) return callPair<A, B>(f);
+    SNB_FFT_PAIRS(X)
+#undef X
+    callPair<0, 0>(f);
+}
+template <typename F> static void forPlanePair(int r1, int r2, F f) {
+#define X(A, B) if (r1 == A && r2 == B) return callPair<A, B>(f);
+    SNB_PLANE_PAIRS(X)
+#undef X
+    callPair<0, 0>(f);
+}
+template <typename F> static void forBool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <typename Real> static BrickGeometry bricksOf(const PmeParams<Real>& p) { return bricksOf(p.d, p.sortNcx, p.sortNcy, p.groupX, p.groupY); }
 
 // Wave priority of the reciprocal pipeline's front kernels (the ones an overlapped step runs beside the resident pair kernel, engine.hip
 // overlapMode).  0 = none: the arbiter then serves the older pair-kernel waves first (measured best, docs/MEASUREMENT_LOG.md round 4).
@@ -48,15 +74,6 @@ struct FastDiv {
     __device__ explicit FastDiv(int d_) : inv(1.0f / (float)d_), d(d_) {}
     __device__ int div(int x) const { return (int)(((float)x + 0.5f) * inv); }
 };
-
-// LDS stride of a z line in k_spreadOwn's region: a stride that is a multiple of 64 dwords puts every line on the same banks (RZ = 64 for
-// sz = 60: lanes = z-neighbours of one column then collide ~13-way: 47.7 us on c3 against 27.8); a few extra values per line spread them
-template <bool FIXED> __host__ __device__ inline int ownLineStride(int RZ) {
-    const int per = FIXED ? 4 : 2;                                  // values per 16 bytes: lines stay 16-byte aligned for the vector copy
-    int st = (RZ + per - 1) / per * per;
-    while (((st * (FIXED ? 1 : 2)) & 7) != 4) st += per;            // stride = 4 (mod 8) dwords: consecutive lines walk over all 64 banks
-    return st;
-}
 
 template <typename Real> struct Cx { Real x, y; };
 template <typename Real, int R1 = 0, int R2 = 0>
@@ -381,26 +398,17 @@ template <typename Real> static int launchSpreadOwn(const PmeParams<Real>& p, hi
 // plane-major for the plane path (launchPmePlanePath replaces forward FFT, convolution and inverse FFT), else 0.
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s) {
     if (p.sortNcx > 0 && p.colRange != nullptr) {
-        const int cx = p.groupX * (p.d.nx / p.sortNcx), cy = p.groupY * (p.d.ny / p.sortNcy);
-        const bool fixed = std::is_same<Real, float>::value && !switches().noFixedSpread && p.d.nz % 2 == 0 && (p.d.nz / p.zSlabs) % 2 == 0;
-        const size_t accBytes = fixed ? sizeof(int) : sizeof(double);
-        const size_t brickBytes = (accBytes * (size_t)cx * cy * (p.d.nz / p.zSlabs) + 15) & ~(size_t)15;
-        const size_t listBytes = sizeof(int) * (fixed ? 8192 : 4096);
-        const int nbz = (cx * cy + 1) / 2;
-        const size_t fftBytes = sizeof(Cx<Real>) * ((size_t)2 * p.d.nz * (nbz + 1) + p.d.nz);
-        const bool fuse = !switches().noFusedZ && p.zSlabs == 1 && brickBytes + std::max(listBytes, fftBytes) <= 64 * 1024;
-        const size_t lds = brickBytes + (fuse ? std::max(listBytes, fftBytes) : listBytes);
-        const int nblocks = p.nsub * (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY) * p.zSlabs;
         if (!p.cellsReady) hipLaunchKernelGGL((k_pmeCells<Real>), dim3((p.natoms + 255) / 256), dim3(256), 0, s, p);
         if (p.ownSlabs > 0) { const int r = launchSpreadOwn<Real>(p, s); if (r >= 0) return r; }
-#define SNB_SPREAD(FX, FZ) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spreadBrick<Real, FX, FZ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                             SNB_STAMPED_LAUNCH(stampSlot(p, 1), (k_spreadBrick<Real, FX, FZ>), dim3(nblocks), dim3(512), lds, s, p); }
+        const BrickSpread q = brickSpread(p.d, bricksOf(p), p.nsub, sizeof(Real), p.zSlabs, switches());
+        auto run = [&](auto FX) {
+            forBool(q.fuse, [&](auto FZ) { launchLds(stampSlot(p, 1), &k_spreadBrick<Real, decltype(FX)::value, decltype(FZ)::value>, dim3(q.blocks), dim3(512), q.lds, s, p); });
+        };
         if constexpr (std::is_same<Real, float>::value) {
-            if (fixed) { if (fuse) SNB_SPREAD(true, true) else SNB_SPREAD(true, false) return fuse ? 1 : 0; }
+            if (q.fixed) { run(std::true_type{}); return q.fuse ? 1 : 0; }
         }
-        if (fuse) SNB_SPREAD(false, true) else SNB_SPREAD(false, false)
-#undef SNB_SPREAD
-        return fuse ? 1 : 0;
+        run(std::false_type{});
+        return q.fuse ? 1 : 0;
     }
     // fallback (triclinic boxes, meshes without a usable column divisor): global float atomics
     launchZeroFill(p.gridReal, sizeof(Real) * (size_t)p.nsub * p.d.nx * p.d.ny * p.d.nz, s);      // (a kernel, not a memset node: misc.hip)
@@ -587,16 +595,6 @@ __device__ __forceinline__ void fftPass2(const Cx<Real>* a, Cx<Real>* bOut, int 
         for (int k2 = 0; k2 < R2; k2++) bOut[(k1 + r1 * k2) * BS + b] = v[k2];
     }
 }
-
-#ifndef SNB_FFT_120
-// the split of a 120-point line, measured on c3 (round 3, A/B through SNB_LIB_PATH): 8 x 15 (rounds 1-2) x kernel 53.2 us, inverse z 16.3,
-// merge + forward z 29.8, y pass 21.3; 10 x 12: 49.7 / 14.8 / 28.2 / 21.6 (the 15-point pass has only nb x 8 tasks for a work-group's 512
-// threads and the most registers); 12 x 10: y pass 28.1; 15 x 8: x kernel 85.4
-#define SNB_FFT_120(X) X(10, 12)
-#endif
-// The kernels are instantiated per (R1, R2) pair (inlining every radix into one runtime switch made them allocate 248 VGPRs);
-// sizes outside this list use the staged Stockham path (R1 = 0).
-#define SNB_FFT_PAIRS(X) X(6, 7) X(6, 9) X(8, 8) X(8, 10) X(9, 10) X(8, 12) X(10, 10) X(9, 12) SNB_FFT_120(X) X(8, 16) X(12, 12) X(10, 16) X(12, 15) X(12, 16) X(15, 16) X(16, 16)
 
 // Runs all stages; returns the buffer holding the result.  Caller must __syncthreads() before reading it.
 template <typename Real, int R1, int R2>
@@ -1401,10 +1399,9 @@ __device__ __forceinline__ void planePass(Cx<Real>* P, const int lines, const in
 struct PlaneNoScale { template <typename... A> __device__ float operator()(A...) const { return 1.0f; } };
 
 // Rectangular planes and square ones without a kernel of their own (round 4): the two axes take splits of their own from the plan at run
-// time (PmePlanDims px1..py2, any product of two of the radices below).  One kernel serves every combination: each pass is a switch over
+// time (PmePlanDims px1..py2, any product of two of the radices of pme_plan.h's SNB_PLANE_RADICES).  One kernel serves every combination: each pass is a switch over
 // the pass bodies per radix -- inlined, it allocates the registers of its largest arm (120 VGPRs, no scratch at 1024 threads; as calls
 // the bodies needed 160 B of stack per lane).  The bodies address LDS through offsets from s_dyn, so they stay ds_ instructions either way.
-#define SNB_PLANE_RADICES(X) X(5) X(6) X(7) X(8) X(9) X(10) X(12) X(15) X(16)
 template <int R, int SIGN, int TWMODE, bool STRIDED, typename PRE>
 __device__ __forceinline__ void planePassCall(const int pOff, const int lines, const int lineStride, const int elemStride, const int other, const int twOff,
                                                         const int tid, const int NT, PRE pre) {
@@ -1689,125 +1686,61 @@ template <int R1, int R2, int NT> __global__ __launch_bounds__(NT) void k_fftZIn
 }
 
 // ---- launch dispatch over the instantiated (R1, R2) pairs ------------------------------------------
+// Every launcher takes its geometry from the planner (pme_plan.h), then dispatches once.
 // threads per work-group of the y FFT pass: 512 over the same LDS tile (two rounds of register sub-transforms become one and twice the
 // waves hide the tile's load latency: 24.4 -> 22.4 us per pass on c3; SNB_FFT_THREADS=256 restores the narrower groups).  The z pass
 // was measured the other way round (16.9 us with 256 threads, 20.9 with 512) and keeps 256.
 static int fftyThreads() { return switches().fftThreads; }
-template <typename Real, bool FWD> static void launchFftZ(int r1, int r2, dim3 grid, size_t lds, hipStream_t s, const PmeParams<Real>& p, int NL) {
-#define X(A, B) if (r1 == A && r2 == B) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZ<Real, FWD, A, B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); SNB_STAMPED_LAUNCH(stampSlot(p, FWD ? 2 : 6), (k_fftZ<Real, FWD, A, B>), grid, dim3(256), lds, s, p, NL); return; }
-    SNB_FFT_PAIRS(X)
-#undef X
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZ<Real, FWD, 0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SNB_STAMPED_LAUNCH(stampSlot(p, FWD ? 2 : 6), (k_fftZ<Real, FWD, 0, 0>), grid, dim3(256), lds, s, p, NL);
+// z: real <-> half complex
+template <typename Real, bool FWD> static void launchFftZ(const PmeParams<Real>& p, hipStream_t s) {
+    const ZPass z = zPass(p.d.nz, sizeof(Real));
+    const size_t nlines = (size_t)p.nsub * p.d.nx * p.d.ny;
+    forFftPair(p.d.rz1, p.d.rz2, [&](auto A, auto B) {
+        launchLds(stampSlot(p, FWD ? 2 : 6), &k_fftZ<Real, FWD, decltype(A)::value, decltype(B)::value>, dim3((unsigned)((nlines + z.NL - 1) / z.NL)), dim3(256), z.lds, s, p, z.NL);
+    });
 }
-template <typename Real> static void launchFftStrided(int r1, int r2, dim3 grid, size_t lds, hipStream_t s, const PmeParams<Real>& p, int n, size_t strideA, int nbTotal, size_t strideK, int NB,
-                                                      int tilesPerA, int sign, int axis) {
-#define X(A, B) if (r1 == A && r2 == B) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftStrided<Real, A, B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); SNB_STAMPED_LAUNCH(axis == 1 ? stampSlot(p, sign < 0 ? 3 : 5) : -1, (k_fftStrided<Real, A, B>), grid, dim3(fftyThreads()), lds, s, p, n, strideA, nbTotal, strideK, NB, tilesPerA, sign, axis); return; }
-    SNB_FFT_PAIRS(X)
-#undef X
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftStrided<Real, 0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SNB_STAMPED_LAUNCH(axis == 1 ? stampSlot(p, sign < 0 ? 3 : 5) : -1, (k_fftStrided<Real, 0, 0>), grid, dim3(fftyThreads()), lds, s, p, n, strideA, nbTotal, strideK, NB, tilesPerA, sign, axis);
+// one strided axis of `batches` slabs: n points per line, `lines` adjacent lines per slab in tiles of t.NB
+template <typename Real> static void launchFftStrided(int r1, int r2, const StridedPass& t, int batches, hipStream_t s, const PmeParams<Real>& p, int n, int lines, int sign, int axis) {
+    forFftPair(r1, r2, [&](auto A, auto B) {
+        launchLds(axis == 1 ? stampSlot(p, sign < 0 ? 3 : 5) : -1, &k_fftStrided<Real, decltype(A)::value, decltype(B)::value>, dim3((unsigned)(batches * t.tilesPerA)), dim3(fftyThreads()), t.lds, s,
+                  p, n, (size_t)n * lines, lines, (size_t)lines, t.NB, t.tilesPerA, sign, axis);
+    });
 }
-template <typename Real> static void launchConvolveX(int r1, int r2, dim3 grid, size_t lds, hipStream_t s, const PmeParams<Real>& p, int NB, int nCols) {
-    if (p.energyOnly) {      // energy-only steps: the same split and thread count as the forces step's kernel, so the Gram sums are the same
-#define X(A, B) if (r1 == A && r2 == B) { \
-        if constexpr (sizeof(Real) == 8 && (A > 12 || B > 12)) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                                                                 SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B, 256, true>), grid, dim3(256), lds, s, p, NB, nCols); } \
-        else { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-               SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B, 512, true>), grid, dim3(512), lds, s, p, NB, nCols); } \
-        return; }
-        SNB_FFT_PAIRS(X)
-#undef X
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, 0, 0, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, 0, 0, 512, true>), grid, dim3(512), lds, s, p, NB, nCols);
-        return;
-    }
-#define X(A, B) if (r1 == A && r2 == B) { \
-        if constexpr (sizeof(Real) == 8 && (A > 12 || B > 12)) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                                                                 SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B, 256>), grid, dim3(256), lds, s, p, NB, nCols); } \
-        else { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, A, B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-               SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, A, B>), grid, dim3(512), lds, s, p, NB, nCols); } \
-        return; }
-    SNB_FFT_PAIRS(X)
-#undef X
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_convolveX<Real, 0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_convolveX<Real, 0, 0>), grid, dim3(512), lds, s, p, NB, nCols);
+template <typename Real> static void launchFftY(const PmeParams<Real>& p, int sign, hipStream_t s) {
+    launchFftStrided<Real>(p.d.ry1, p.d.ry2, yPass(p.d, sizeof(Real), switches()), p.nsub * p.d.nx, s, p, p.d.ny, p.d.nzc, sign, 1);
 }
 
-
-// Plane path (k_planeXY + k_fftZInvMix): single precision, a square mesh plane that fits LDS with its row padding, an instantiated
-// two-pass split, at most 8 held subsets, and the own-atoms spreader's merge kernel in front (it writes the plane-major spectrum).
-#define SNB_PLANE_PAIRS(X) X(6, 7) X(6, 9) X(8, 8) X(8, 10) X(9, 10) X(8, 12) X(10, 10) X(9, 12) X(10, 12) X(8, 16)
-// square plane with a split that has a kernel of its own (static splits: no calls, one table of roots); everything else takes the run-time kernel
-static bool planeSquare(const PmePlanDims& d) {
-    if (switches().planeDynamic || d.nx != d.ny || d.px1 != d.py1 || d.px2 != d.py2) return false;
-#define X(A, B) if (d.px1 == A && d.px2 == B) return true;
-    SNB_PLANE_PAIRS(X)
-#undef X
-    return false;
-}
-bool planeIsStatic(const PmePlanDims& d) { return planeSquare(d); }
-template <typename Real> static size_t planeLds(const PmeParams<Real>& p) { return sizeof(Cx<Real>) * ((size_t)p.d.nx * (p.d.ny | 1) + p.d.nx + (planeSquare(p.d) ? 0 : p.d.ny)); }
-template <typename Real> static bool planePathOK(const PmeParams<Real>& p) {
-    if (switches().noPlaneFft || !std::is_same<Real, float>::value || !p.planeB || !p.planeEterm) return false;
-    if ((p.d.ny & 1) || p.d.px1 <= 0 || p.d.py1 <= 0 || p.d.px1 * p.d.px2 != p.d.nx || p.d.py1 * p.d.py2 != p.d.ny) return false;
-    if (p.nsub > 8 || planeLds(p) > 156 * 1024) return false;
-    return planeSquare(p.d) || !switches().noRectPlanes;
-}
-// y lines per work-group of the inverse z kernel = tile of the convolved planes' layout (c4, 8 subsets: plane + z kernel 45.5 + 55.0 us with 8, 61.2 + 42.4 with 4: 32-byte runs in the plane kernel's store)
-static int planeTileY(const PmeParams<float>& p) {
-    const int env = switches().zmixNby;
-    return (env == 2 || env == 4 || env == 8) ? env : 8;
-}
+template <typename Real> static bool planePathOK(const PmeParams<Real>& p) { return p.planeB && p.planeEterm && planePath(p.d, p.nsub, sizeof(Real), switches()).ok; }
 static void launchPlaneXY(const PmeParams<float>& p, hipStream_t s) {
-    const size_t lds = planeLds(p);
-    const int NBY = planeTileY(p);
+    const PlanePath q = planePath(p.d, p.nsub, sizeof(float), switches());
+    const int NBY = planeTileY(switches());
     const dim3 grid((unsigned)(p.nsub * p.d.nzc));
+    const bool square = planeSquare(p.d, switches());      // (else: the kernel with run-time splits)
     if (p.energyOnly) {      // energy-only steps: 1024 threads, the static split of a square plane or the run-time one
-#define X(A, B) if (planeSquare(p.d) && p.d.px1 == A && p.d.px2 == B) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<A, B, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                                                                    SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<A, B, 1024, true>), grid, dim3(1024), lds, s, p, NBY); return; }
-        SNB_PLANE_PAIRS(X)
-#undef X
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<0, 0, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<0, 0, 1024, true>), grid, dim3(1024), lds, s, p, NBY);
+        forPlanePair(square ? p.d.px1 : 0, square ? p.d.px2 : 0, [&](auto A, auto B) {
+            launchLds(stampSlot(p, 4), &k_planeXY<decltype(A)::value, decltype(B)::value, 1024, true>, grid, dim3(1024), q.lds, s, p, NBY);
+        });
         return;
     }
-    const int nt = switches().planeNt;
-    if (!planeSquare(p.d)) {      // rectangular plane: the kernel with run-time splits
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<0, 0, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<0, 0, 1024>), grid, dim3(1024), lds, s, p, NBY);
-        return;
-    }
-#define X(A, B) if (p.d.px1 == A && p.d.px2 == B) { \
-        if (nt == 768) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<A, B, 768>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                         SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<A, B, 768>), grid, dim3(768), lds, s, p, NBY); } \
-        else { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_planeXY<A, B, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-               SNB_STAMPED_LAUNCH(stampSlot(p, 4), (k_planeXY<A, B, 1024>), grid, dim3(1024), lds, s, p, NBY); } \
-        return; }
-    SNB_PLANE_PAIRS(X)
-#undef X
+    if (!square) { launchLds(stampSlot(p, 4), &k_planeXY<0, 0, 1024>, grid, dim3(1024), q.lds, s, p, NBY); return; }
+    forPlanePair(p.d.px1, p.d.px2, [&](auto A, auto B) {      // (a square plane's split is one of the list)
+        constexpr int a = decltype(A)::value, b = decltype(B)::value;
+        if constexpr (a > 0) {
+            if (q.threads == 768) { launchLds(stampSlot(p, 4), &k_planeXY<a, b, 768>, grid, dim3(768), q.lds, s, p, NBY); return; }
+        }
+        launchLds(stampSlot(p, 4), &k_planeXY<a, b, 1024>, grid, dim3(1024), q.lds, s, p, NBY);
+    });
 }
 static void launchFftZInvMix(const PmeParams<float>& p, hipStream_t s) {
-    const int NP = (p.nsub + 1) / 2;
-    const int NBY = planeTileY(p);
-    bool twoPass = false;
-#define X(A, B) if (p.d.rz1 == A && p.d.rz2 == B) twoPass = true;
-    SNB_FFT_PAIRS(X)
-#undef X
-    const size_t lds = sizeof(Cx<float>) * ((size_t)(twoPass ? 1 : 2) * p.d.nz * (NBY * NP + 1) + p.d.nz);      // (in place with a two-pass split)
-    const dim3 grid((unsigned)(p.d.nx * ((p.d.ny + NBY - 1) / NBY)));
-    const int ntEnv = switches().zmixNt;
-    const bool wide = ntEnv ? ntEnv == 512 : NBY * NP >= 24;      // 24+ complex transforms per work-group (5-8 subsets): 512 threads
-#define X(A, B) if (p.d.rz1 == A && p.d.rz2 == B) { \
-        if (wide) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZInvMix<A, B, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                    SNB_STAMPED_LAUNCH(stampSlot(p, 6), (k_fftZInvMix<A, B, 512>), grid, dim3(512), lds, s, p, NBY); } \
-        else { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZInvMix<A, B, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-               SNB_STAMPED_LAUNCH(stampSlot(p, 6), (k_fftZInvMix<A, B, 256>), grid, dim3(256), lds, s, p, NBY); } \
-        return; }
-    SNB_FFT_PAIRS(X)
-#undef X
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fftZInvMix<0, 0, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SNB_STAMPED_LAUNCH(stampSlot(p, 6), (k_fftZInvMix<0, 0, 256>), grid, dim3(256), lds, s, p, NBY);
+    const ZMix z = zMix(p.d, p.nsub, switches());
+    const dim3 grid((unsigned)(p.d.nx * ((p.d.ny + z.NBY - 1) / z.NBY)));
+    forFftPair(p.d.rz1, p.d.rz2, [&](auto A, auto B) {
+        constexpr int a = decltype(A)::value, b = decltype(B)::value;
+        if constexpr (a > 0) {
+            if (z.threads == 512) { launchLds(stampSlot(p, 6), &k_fftZInvMix<a, b, 512>, grid, dim3(512), z.lds, s, p, z.NBY); return; }
+        }
+        launchLds(stampSlot(p, 6), &k_fftZInvMix<a, b, 256>, grid, dim3(256), z.lds, s, p, z.NBY);
+    });
 }
 // Rebuild time: the kernel-value table of the plane path (no-op when the mesh does not qualify).
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s) {      // true: the table was (re)filled
@@ -1830,102 +1763,39 @@ template void launchPmePlanePath<float>(const PmeParams<float>&, hipStream_t);
 template void launchPmePlanePath<double>(const PmeParams<double>&, hipStream_t);
 
 // own-atoms spreader: k_spreadOwn over (brick, slab) work-groups, then k_spreadMerge per brick (fused with the forward z FFT when its
-// buffers fit LDS).  Geometry (slabs, margin) and the buffers come from the engine (sized at rebuild time).
+// buffers fit LDS).  The engine sized the buffers at rebuild time from the same plan (pme_plan.h ownSpread: same mesh, bricks and margin).
 template <typename Real> static int launchSpreadOwn(const PmeParams<Real>& p, hipStream_t s) {
-    if (switches().noOwnSpread || p.ownSlabs < 2 || !p.ownPartial || p.d.nz > 256) return -1;      // (one slab's region of nz + 4 planes would wrap onto itself)
-    const int cx = p.groupX * (p.d.nx / p.sortNcx), cy = p.groupY * (p.d.ny / p.sortNcy);
-    const int sz = p.d.nz / p.ownSlabs;
-    if (sz & 1) return -1;      // (the regions are copied 8 or 16 bytes at a time)
-    const bool fixed = std::is_same<Real, float>::value && !switches().noFixedSpread;
-    const int RX = cx + 4 + 2 * p.ownMargin, RY = cy + 4 + 2 * p.ownMargin, RZ = sz + 4;
-    const size_t ldsOwn = (fixed ? sizeof(int) : sizeof(double)) * (size_t)RX * RY * (fixed ? ownLineStride<true>(RZ) : ownLineStride<false>(RZ));
-    const int M = p.ownMargin;
-    const int reachX = (4 + M + cx - 1) / cx + (M + cx - 1) / cx + 1, reachY = (4 + M + cy - 1) / cy + (M + cy - 1) / cy + 1;      // bricks whose regions cover a line
-    if (ldsOwn > 64 * 1024 || RX > p.d.nx || RY > p.d.ny || p.groupX * p.groupY > 16 || reachX > 3 || reachY > 3 || p.ownSlabs > 32 || sz < 4) return -1;
-    if ((size_t)p.nsub * (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY) * p.ownSlabs * RX * RY * RZ >= ((size_t)1 << 31)) return -1;      // (the merge kernel keeps 32-bit element offsets into ownPartial)
-    const int cmax = fixed ? 4 : 2, chunk = (sz % cmax == 0) ? cmax : ((fixed && sz % 2 == 0) ? 2 : 1);      // values per load of the merge kernel (16, 8 or 4 bytes)
-    const int nbricks = p.nsub * (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY);
-    const int nb = (cx * cy + 1) / 2;
-    const size_t ldsFft = sizeof(Cx<Real>) * ((size_t)2 * p.d.nz * (nb + 1) + p.d.nz);
-    const bool fuse = !switches().noFusedZ && ldsFft <= 120 * 1024;
-    const int plane = (fuse && planePathOK<Real>(p)) ? 1 : 0;      // plane-major spectrum for k_planeXY
-#define SNB_OWN(FX) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spreadOwn<Real, FX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOwn); \
-                      SNB_STAMPED_LAUNCH(stampSlot(p, 1), (k_spreadOwn<Real, FX>), dim3(nbricks * p.ownSlabs), dim3(512), ldsOwn, s, p); }
-    // a long mesh in double precision gives a 256-thread work-group a dozen 16-byte chunks per thread, each three rounds of dependent loads
-    // (c5, 180^3: 309 us): 512 threads there
-    const int mergeNt = switches().mergeNt;
-    const bool wideMerge = mergeNt ? mergeNt == 512 : (size_t)cx * cy * (p.d.nz / chunk) > 6 * 256;
-#define SNB_MERGE(FX, FZ, A, B) { if (wideMerge) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spreadMerge<Real, FX, FZ, A, B, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FZ ? ldsFft : 0)); \
-                                      SNB_STAMPED_LAUNCH(stampSlot(p, 2), (k_spreadMerge<Real, FX, FZ, A, B, 512>), dim3(nbricks), dim3(512), (FZ ? ldsFft : 0), s, p, chunk, plane); } \
-                                  else { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spreadMerge<Real, FX, FZ, A, B, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FZ ? ldsFft : 0)); \
-                                      SNB_STAMPED_LAUNCH(stampSlot(p, 2), (k_spreadMerge<Real, FX, FZ, A, B, 256>), dim3(nbricks), dim3(256), (FZ ? ldsFft : 0), s, p, chunk, plane); } }
-    bool done = false;
+    const BrickGeometry b = bricksOf(p);
+    const OwnSpread o = ownSpread(p.d, b, p.nsub, sizeof(Real), p.ownMargin, switches());
+    if (!o.runs || o.slabs != p.ownSlabs || !p.ownPartial) return -1;      // (ownPartial holds the regions of the engine's plan, no others)
+    const int plane = (o.plane && p.planeB && p.planeEterm) ? 1 : 0;      // plane-major spectrum for k_planeXY
+    const int nbricks = p.nsub * b.count();
+    auto run = [&](auto FX) {
+        constexpr bool fx = decltype(FX)::value;
+        launchLds(stampSlot(p, 1), &k_spreadOwn<Real, fx>, dim3(nbricks * o.slabs), dim3(512), o.ldsOwn, s, p);
+        auto merge = [&](auto FZ, auto A, auto B) {
+            constexpr bool fz = decltype(FZ)::value;
+            forBool(o.mergeThreads == 512, [&](auto W) {
+                constexpr int NT = decltype(W)::value ? 512 : 256;
+                launchLds(stampSlot(p, 2), &k_spreadMerge<Real, fx, fz, decltype(A)::value, decltype(B)::value, NT>, dim3(nbricks), dim3(NT), fz ? o.ldsFft : 0, s, p, o.chunk, plane);
+            });
+        };
+        if (o.fuse) forFftPair(p.d.rz1, p.d.rz2, [&](auto A, auto B) { merge(std::true_type{}, A, B); });
+        else merge(std::false_type{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    };
     if constexpr (std::is_same<Real, float>::value) {
-        if (fixed) {
-            SNB_OWN(true)
-            if (fuse) {
-#define X(A, B) if (!done && p.d.rz1 == A && p.d.rz2 == B) { SNB_MERGE(true, true, A, B) done = true; }
-                SNB_FFT_PAIRS(X)
-#undef X
-                if (!done) { SNB_MERGE(true, true, 0, 0) done = true; }
-            } else { SNB_MERGE(true, false, 0, 0) done = true; }
-        }
+        if (o.fixed) { run(std::true_type{}); return plane ? 2 : (o.fuse ? 1 : 0); }
     }
-    if (!done) {
-        SNB_OWN(false)
-        if (fuse) {
-#define X(A, B) if (!done && p.d.rz1 == A && p.d.rz2 == B) { SNB_MERGE(false, true, A, B) done = true; }
-            SNB_FFT_PAIRS(X)
-#undef X
-            if (!done) { SNB_MERGE(false, true, 0, 0) done = true; }
-        } else { SNB_MERGE(false, false, 0, 0) }
-    }
-#undef SNB_OWN
-#undef SNB_MERGE
-    return plane ? 2 : (fuse ? 1 : 0);
+    run(std::false_type{});
+    return plane ? 2 : (o.fuse ? 1 : 0);
 }
 
-static size_t ldsBudget() { return 96 * 1024; }
-
-template <typename Real> static int pickBatch(size_t bytesPerBatchElem, int maxB, int minB = 1) {
-    int b = (int)(ldsBudget() / bytesPerBatchElem);
-    if (b > maxB) b = maxB;
-    if (b < minB) b = minB;
-    return b;
-}
-
-// Columns per work-group of the y pass.  Single precision: as many as fit the LDS budget, at most 32 (c3: 32 + 29 columns 27.8 us, three
-// tiles of 21 28.4).  Double precision (round 3): at least three tiles of even width -- 90^3 (46 columns) 16 + 16 + 14: 16.5 / 14.9 us per
-// pass against 21.5 / 20.6 for 32 + 14; 180^3 six tiles of 16: 139 / 128 against 145 / 133 for 17 x 5 + 6; 120^3 keeps three tiles
-// (four tiles of 16: 48.6 against 40.8)
-template <typename Real> static int fftyBatch(int ny, int nzc, int forced) {
-    const int cap = pickBatch<Real>((size_t)2 * ny * sizeof(Cx<Real>), forced > 0 ? forced : 32);
-    if (forced > 0 || sizeof(Real) == 4) return cap;
-    const int tiles = (nzc + cap - 1) / cap;
-    if (tiles < 3 && nzc >= 24) return (nzc + 2) / 3;
-    return cap > 2 ? (cap & ~1) : cap;      // (balanced tiles of 21 on the 120^3 mesh: 42.6 us against 40.8 for 25 + 25 + 11)
-}
 template <typename Real> void launchPmeForwardFFT(const PmeParams<Real>& p, hipStream_t s, bool zDone) {
-    const int nx = p.d.nx, ny = p.d.ny, nz = p.d.nz, nzc = p.d.nzc;
-    // z: real -> half complex (unless the brick spreader already did it)
-    if (!zDone) {
-        int NC = pickBatch<Real>((size_t)2 * nz * sizeof(Cx<Real>), 17) - 1;   // complex lines per work-group (two real lines each)
-        NC &= ~1;
-        if (NC < 2) NC = 2;
-        const int NL = 2 * NC;
-        const size_t lds = (size_t)2 * nz * (NC + 1) * sizeof(Cx<Real>) + (size_t)nz * sizeof(Cx<Real>);
-        const size_t nlines = (size_t)p.nsub * nx * ny;
-        launchFftZ<Real, true>(p.d.rz1, p.d.rz2, dim3((unsigned)((nlines + NL - 1) / NL)), lds, s, p, NL);
-    }
-    // y
-    {
-        const int NB = fftyBatch<Real>(ny, nzc, switches().fftyNb);
-        const size_t lds = (size_t)2 * ny * NB * sizeof(Cx<Real>) + (size_t)ny * sizeof(Cx<Real>);
-        const int tilesPerA = (nzc + NB - 1) / NB;
-        launchFftStrided<Real>(p.d.ry1, p.d.ry2, dim3((unsigned)(p.nsub * nx * tilesPerA)), lds, s, p, ny, (size_t)ny * nzc, nzc, (size_t)nzc, NB, tilesPerA, -1, 1);
-    }
+    if (!zDone) launchFftZ<Real, true>(p, s);      // (unless the brick spreader already did it)
+    launchFftY<Real>(p, -1, s);
 }
 
+// fused x-axis kernel
 template <typename Real> void launchPmeConvolution(const PmeParams<Real>& p, hipStream_t s) {
     const int nx = p.d.nx;
     const int nCols = p.d.ny * p.d.nzc;
@@ -1940,35 +1810,25 @@ template <typename Real> void launchPmeConvolution(const PmeParams<Real>& p, hip
             l[0] = nx; l[1] = p.nsub; l[2] = NB;
         }
     }
-    launchConvolveX<Real>(p.d.rx1, p.d.rx2, dim3((unsigned)((nCols + NB - 1) / NB)), c.total, s, p, NB, nCols);
+    // energy-only steps: the same split and thread count as the forces step's kernel, so the Gram sums are the same
+    forBool(p.energyOnly != 0, [&](auto E) {
+        forFftPair(p.d.rx1, p.d.rx2, [&](auto A, auto B) {
+            constexpr int a = decltype(A)::value, b = decltype(B)::value, NT = convxThreads(a, b, sizeof(Real));
+            launchLds(stampSlot(p, 4), &k_convolveX<Real, a, b, NT, decltype(E)::value>, dim3((unsigned)((nCols + NB - 1) / NB)), dim3(NT), c.total, s, p, NB, nCols);
+        });
+    });
 }
 
 template <typename Real> void launchPmeInverseFFT(const PmeParams<Real>& p, hipStream_t s) {
-    const int nx = p.d.nx, ny = p.d.ny, nz = p.d.nz, nzc = p.d.nzc;
-    {
-        const int NB = fftyBatch<Real>(ny, nzc, switches().fftyNb);
-        const size_t lds = (size_t)2 * ny * NB * sizeof(Cx<Real>) + (size_t)ny * sizeof(Cx<Real>);
-        const int tilesPerA = (nzc + NB - 1) / NB;
-        launchFftStrided<Real>(p.d.ry1, p.d.ry2, dim3((unsigned)(p.nsub * nx * tilesPerA)), lds, s, p, ny, (size_t)ny * nzc, nzc, (size_t)nzc, NB, tilesPerA, +1, 1);
-    }
-    {
-        int NC = pickBatch<Real>((size_t)2 * nz * sizeof(Cx<Real>), 17) - 1;   // complex lines per work-group (two real lines each)
-        NC &= ~1;
-        if (NC < 2) NC = 2;
-        const int NL = 2 * NC;
-        const size_t lds = (size_t)2 * nz * (NC + 1) * sizeof(Cx<Real>) + (size_t)nz * sizeof(Cx<Real>);
-        const size_t nlines = (size_t)p.nsub * nx * ny;
-        launchFftZ<Real, false>(p.d.rz1, p.d.rz2, dim3((unsigned)((nlines + NL - 1) / NL)), lds, s, p, NL);
-    }
+    launchFftY<Real>(p, +1, s);
+    launchFftZ<Real, false>(p, s);
 }
 
 // x axis alone (used by the FFT unit-test hook; the pipeline itself uses the fused k_convolveX)
 template <typename Real> void launchPmeFFTX(const PmeParams<Real>& p, int sign, hipStream_t s) {
     const int nx = p.d.nx, nCols = p.d.ny * p.d.nzc;
-    const int NB = pickBatch<Real>((size_t)2 * nx * sizeof(Cx<Real>), 16);
-    const size_t lds = (size_t)2 * nx * NB * sizeof(Cx<Real>) + (size_t)nx * sizeof(Cx<Real>);
-    const int tilesPerA = (nCols + NB - 1) / NB;
-    launchFftStrided<Real>(p.d.rx1, p.d.rx2, dim3((unsigned)(p.nsub * tilesPerA)), lds, s, p, nx, (size_t)nx * nCols, nCols, (size_t)nCols, NB, tilesPerA, sign, 0);
+    const StridedPass t = stridedPass(nx, nCols, sizeof(Real), pickBatch((size_t)2 * nx * sizeof(Cx<Real>), 16));
+    launchFftStrided<Real>(p.d.rx1, p.d.rx2, t, p.nsub, s, p, nx, nCols, sign, 0);
 }
 template void launchPmeFFTX<float>(const PmeParams<float>&, int, hipStream_t);
 template void launchPmeFFTX<double>(const PmeParams<double>&, int, hipStream_t);
@@ -2310,78 +2170,25 @@ template <typename Real, int NT, bool CTX> __global__ __launch_bounds__(NT) void
     SNB_TRACE_END(p.stepTrace, 12);
 }
 
-template <typename Real> static bool launchInterpolateBricks(const PmeParams<Real>& p0, hipStream_t s) {
+template <typename Real> bool launchPmeInterpolate(const PmeParams<Real>& p0, hipStream_t s) {
+    if (p0.natoms <= 0) return false;
     PmeParams<Real> p = p0;
-    {
-        const int cx = p.groupX * (p.d.nx / p.sortNcx), cy = p.groupY * (p.d.ny / p.sortNcy);
-        const int zsEnv = switches().interpZSlabs;
-        int zSlabs = 1;      // measured on c3: 1 slab 52 us, 2 slabs 70, 4 slabs 72 (every slab rescans the columns' atoms)
-        if (zsEnv > 0 && p.d.nz % zsEnv == 0 && p.d.nz / zsEnv >= 8) zSlabs = zsEnv;
-        auto ldsFor = [&](int slabs) { return ((sizeof(Real) * (size_t)(cx + 6) * (cy + 6) * (p.d.nz / slabs + 4) + 15) & ~(size_t)15) + sizeof(double) * p.nsubTotal * (p.nsubTotal + 1); };
-        // a brick that does not fit LDS in one piece (double precision on a large mesh: 12 x 12 x 184 doubles = 212 KB for the 180^3 mesh of
-        // c5) is cut into the fewest z slabs that do, rather than falling back to the 32-lanes-per-atom gather kernel (424 us there)
-        if (zsEnv <= 0) for (int k = 2; k <= 8 && ldsFor(zSlabs) > 150 * 1024; k++) if (p.d.nz % k == 0 && p.d.nz / k >= 8) zSlabs = k;
-        // few, wide bricks (a coarse mesh whose bricks span 2 x 2 sort columns: the 60^3 dispersion mesh of c3l has 100 of them, 3000 atoms
-        // each, on 256 CUs: 58.8 us against 26.6 for the 120^3 Coulomb mesh): slabs buy work-groups; every slab rescans the bricks' atoms,
-        // which is why the fine mesh (400 bricks) does not take them
-        if (zsEnv <= 0 && zSlabs == 1) {
-            const int nb1 = (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY);
-            for (int k = 2; k <= 6 && nb1 * zSlabs < 192; k++) if (p.d.nz % k == 0 && p.d.nz / k >= 10) zSlabs = k;
-        }
-        const size_t lds = ldsFor(zSlabs);
-        if (lds <= 150 * 1024 && !switches().noInterpBricks && p.nsubTotal * p.groupX * p.groupY <= 256) {
-            const int nblocks = (p.sortNcx / p.groupX) * (p.sortNcy / p.groupY) * zSlabs;
+    if (p.sortNcx > 0 && p.colRange != nullptr) {
+        const BrickGeometry b = interpWiden(p.d, bricksOf(p), p.nsubTotal, sizeof(Real), switches());
+        p.groupX = b.gx; p.groupY = b.gy;
+        const InterpBricks q = interpBricks(p.d, b, p.nsubTotal, sizeof(Real), switches());
+        if (q.bricks) {
             if (!p.mix) p.outForces = nullptr;      // (sharded engines visit an atom once per held grid: the separate finish pass stays)
-            // 512-thread work-groups go two to a CU when the brick fits LDS twice (the kernel's ~100 VGPRs allow 16 waves per CU either way):
-            // with more bricks than CUs the second round of 1024-thread groups runs half empty
-            const int ntEnv = switches().interpThreads;
-            const bool narrow = ntEnv ? ntEnv == 512 : (nblocks > 256 && lds <= 76 * 1024);
             if (!p.outForces) p.userToCtx = nullptr;
-            if (p.userToCtx) {      // bound context
-                if (narrow) {
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 512, true>), dim3(nblocks), dim3(512), lds, s, p, zSlabs);
-                } else {
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 1024, true>), dim3(nblocks), dim3(1024), lds, s, p, zSlabs);
-                }
-            } else if (narrow) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 512, false>), dim3(nblocks), dim3(512), lds, s, p, zSlabs);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_interpolateBricks<Real, 1024, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolateBricks<Real, 1024, false>), dim3(nblocks), dim3(1024), lds, s, p, zSlabs);
-            }
+            forBool(p.userToCtx != nullptr, [&](auto CTX) {      // bound context
+                constexpr bool ctx = decltype(CTX)::value;
+                if (q.threads == 512) launchLds(stampSlot(p, 7), &k_interpolateBricks<Real, 512, ctx>, dim3(q.blocks), dim3(512), q.lds, s, p, q.zSlabs);
+                else launchLds(stampSlot(p, 7), &k_interpolateBricks<Real, 1024, ctx>, dim3(q.blocks), dim3(1024), q.lds, s, p, q.zSlabs);
+            });
             return p.outForces != nullptr;
         }
     }
-    const size_t lds = (!p.mix && p.wantEnergy) ? sizeof(double) * p.nsubTotal * (p.nsubTotal + 1) : 0;
-    SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolate<Real>), dim3((p.natoms + 7) / 8), dim3(256), lds, s, p);
-    return false;
-}
-
-template <typename Real> bool launchPmeInterpolate(const PmeParams<Real>& p, hipStream_t s) {
-    if (p.natoms <= 0) return false;
-    if (p.sortNcx > 0 && p.colRange != nullptr) {
-        // The kernel needs ~100 VGPRs, so one 1024-thread work-group occupies a CU: with more bricks than CUs the launch runs in rounds.
-        // Wider bricks (2 x 1, 2 x 2 columns) cut the count below the CU count and the halo overhead with it, as long as LDS allows.
-        PmeParams<Real> q = p;
-        const int gEnv = switches().interpGroup;
-        // (measured on c3, 400 single-column bricks: 1024 threads on 2 x 1-column bricks 35.2 us, 1024 threads on single columns 39.3,
-        // 512 threads on single columns -- two work-groups per CU -- 29.1: when the single-column brick fits LDS twice, do not widen)
-        const size_t single = sizeof(Real) * (size_t)(q.groupX * (q.d.nx / q.sortNcx) + 6) * (q.groupY * (q.d.ny / q.sortNcy) + 6) * (q.d.nz + 4) + 1024;
-        for (int step = 0; step < 2; step++) {
-            const int nb = (q.sortNcx / q.groupX) * (q.sortNcy / q.groupY);
-            if (gEnv >= 0 ? step >= gEnv : (nb <= 256 || single <= 76 * 1024)) break;
-            PmeParams<Real> t = q;
-            if (step == 0 && t.sortNcx % (2 * t.groupX) == 0) t.groupX *= 2; else if (t.sortNcy % (2 * t.groupY) == 0) t.groupY *= 2; else break;
-            const size_t need = sizeof(Real) * (size_t)(t.groupX * (t.d.nx / t.sortNcx) + 6) * (t.groupY * (t.d.ny / t.sortNcy) + 6) * (t.d.nz + 4) + 1024;
-            if (need > 150 * 1024 || t.nsubTotal * t.groupX * t.groupY > 256) break;
-            q = t;
-        }
-        return launchInterpolateBricks<Real>(q, s);
-    }
-    const size_t lds = (!p.mix && p.wantEnergy) ? sizeof(double) * p.nsubTotal * (p.nsubTotal + 1) : 0;
+    const size_t lds = (!p.mix && p.wantEnergy) ? sizeof(double) * p.nsubTotal * (p.nsubTotal + 1) : 0;      // 32 lanes per atom
     SNB_STAMPED_LAUNCH(stampSlot(p, 7), (k_interpolate<Real>), dim3((p.natoms + 7) / 8), dim3(256), lds, s, p);
     return false;
 }
@@ -2396,55 +2203,5 @@ template void launchPmeInverseFFT<float>(const PmeParams<float>&, hipStream_t);
 template void launchPmeInverseFFT<double>(const PmeParams<double>&, hipStream_t);
 template bool launchPmeInterpolate<float>(const PmeParams<float>&, hipStream_t);
 template bool launchPmeInterpolate<double>(const PmeParams<double>&, hipStream_t);
-
-// ---- host helpers ---------------------------------------------------------------------------------
-bool factorize(int n, int* factors, int* nf) {
-    int k = 0;
-    while (n % 4 == 0) { factors[k++] = 4; n /= 4; }
-    while (n % 2 == 0) { factors[k++] = 2; n /= 2; }
-    while (n % 3 == 0) { factors[k++] = 3; n /= 3; }
-    while (n % 5 == 0) { factors[k++] = 5; n /= 5; }
-    while (n % 7 == 0) { factors[k++] = 7; n /= 7; }
-    while (n % 11 == 0) { factors[k++] = 11; n /= 11; }      // 11 and 13: the reference's GPU FFT is legal up to 13-smooth sizes
-    while (n % 13 == 0) { factors[k++] = 13; n /= 13; }      // (platforms/common/include/FFT3DFactory.h:45-47)
-    *nf = k;
-    return n == 1 && k <= 16;
-}
-
-// n = r1 * r2 for one of the instantiated (R1, R2) pairs; false (and 0, 0) if n is not in the list
-// plane path: n = r1 * r2 with both factors among the radices k_planeXY has pass bodies for, r1 <= r2, the most balanced pair; the
-// pairs with a kernel of their own (SNB_PLANE_PAIRS) first
-bool splitPlane(int n, int* r1, int* r2) {
-#define X(A, B) if (n == (A) * (B)) { *r1 = A; *r2 = B; return true; }
-    SNB_PLANE_PAIRS(X)
-#undef X
-    const int radices[] = {
-#define X(A) A,
-        SNB_PLANE_RADICES(X)
-#undef X
-    };
-    int best = 0;
-    for (int a : radices) for (int b : radices) if (a <= b && a * b == n && a > best) { best = a; *r1 = a; *r2 = b; }
-    if (best) return true;
-    *r1 = *r2 = 0;
-    return false;
-}
-
-bool splitTwoPass(int n, int* r1, int* r2) {
-#define X(A, B) if (n == (A) * (B)) { *r1 = A; *r2 = B; return true; }
-    SNB_FFT_PAIRS(X)
-#undef X
-    *r1 = *r2 = 0;
-    return false;
-}
-
-int legalGridSize(int n) {
-    if (n < 6) n = 6;
-    for (;; n++) {
-        int f[32], nf, m = n;
-        for (int p : {2, 3, 5, 7, 11, 13}) while (m % p == 0) m /= p;
-        if (m == 1 && factorize(n, f, &nf)) return n;
-    }
-}
 
 }  // namespace snb

@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+#include "pme_plan.h"      // PmePlanDims, the FFT splits, the planner of the reciprocal path (host only)
+
 #define SNB_ONE_4PI_EPS0 138.93545764438198
 #define SNB_PI 3.14159265358979323846
 #define SNB_EPSILON0 (1.0 / (4.0 * SNB_PI * SNB_ONE_4PI_EPS0))
@@ -123,14 +125,6 @@ template <typename Real> struct PairListParams {  // 1-4 exceptions: one thread 
     Real alpha, alphaD;
     double alpha64;           // the Ewald alpha unrounded (energy evaluations of the exclusion corrections run in double)
     int ljpme;
-};
-
-struct PmePlanDims {
-    int nx, ny, nz, nzc;      // nzc = nz/2+1
-    int nfx, nfy, nfz;        // number of radix factors per axis
-    int fx[16], fy[16], fz[16];
-    int rx1, rx2, ry1, ry2, rz1, rz2;   // two-pass register-FFT split n = r1*r2 per axis (0 = use the staged Stockham path)
-    int px1, px2, py1, py2;             // plane path (pme.hip k_planeXY): splits of the x and y axes into radices it has pass bodies for (0 = none)
 };
 
 // Per-kernel begin/end stamps of a timed (eager) step: the engine points g_stamps at a set of event pairs before it enqueues the step;
@@ -479,11 +473,5 @@ void launchParticleParams(int n, int nsub, const double* base, const int* offSta
 template <typename Real>
 void launchExceptionParams(int n, const double* base, const int* offStart, const int* offGlobal, const double* offDelta, const double* globals, const int* slice,
                            typename Vec<Real>::T4* out, hipStream_t s);
-
-int legalGridSize(int n);
-bool factorize(int n, int* factors, int* nfactors);
-bool splitTwoPass(int n, int* r1, int* r2);
-bool splitPlane(int n, int* r1, int* r2);
-bool planeIsStatic(const PmePlanDims& d);      // a square plane whose split has a plane kernel of its own (pme.hip planeSquare)
 
 }  // namespace snb

@@ -1,19 +1,20 @@
 """The mesh-size census: a table of PME meshes that between them reach every (R1, R2) instantiation of the reciprocal path's six kernel
-families (pme.hip: the macro lists of FFT pairs, plane pairs and plane radices), on one set of atoms (tests/test_mesh_census.py on the CPU,
+families (csrc/pme_plan.h: the macro lists of FFT pairs, plane pairs and plane radices), on one set of atoms (tests/test_mesh_census.py on the CPU,
 tests/test_gpu_mesh_census.py on the GPU).  It sits on tests/recip_systems.py: same oracle, same comparison, same bars.
 
 The atoms are the lattice of `ortho` (13 608 atoms in 5.6 x 6.4 x 7.2 nm, alpha 2.6283) in 2 or in 5 slabs along y.  The mesh of a row does not
 follow the cell's proportions: engine and oracle share it, so a coarse or a fine axis only moves the error both have in common.
 
-Where a row's splits come from.  The table does not compute splitTwoPass / splitPlane (pme.hip): every row STATES the splits it is there for,
+Where a row's splits come from.  The table does not compute splitTwoPass / splitPlane (csrc/pme_plan.h): every row STATES the splits it is there for,
 in the words of the engine's own SNB_VERBOSE mesh line (engine.hip describeMesh: "fft splits x a*b y a*b z a*b, plane splits x a*b y a*b
 (static | run-time | none)"), and the GPU leg asserts that the engine printed exactly that for the row.  The CPU leg reduces the stated splits
-to kernel keys and holds them against the kernel names in the built gfx950 code objects.
+to kernel keys and holds them against the kernel names in the built gfx950 code objects, and runs the engine's planner itself
+(tests/pme_plan_check.cpp) against the stated splits.
 
 What the splits do not settle -- which pipeline a mesh gets, whether the merge kernel fuses the z pass, the thread counts -- follows from sizes
-and LDS budgets; plan() below repeats that arithmetic (host_lists.h sortColumns; engine.hip brickGeometry, planOwnSpread; pme.hip
-launchSpreadOwn, planePathOK, launchFftZInvMix, launchConvolveX) and the GPU leg checks the part of it that shows: the sort columns, the
-planned spreader and its slabs from the mesh line, the pipeline from the stamp slots.
+and LDS budgets; plan() below repeats that arithmetic (host_lists.h sortColumns; csrc/pme_plan.h brickGeometry, ownSpreadMargin,
+ownSpread, planePath, zMix, convxThreads).  The CPU leg holds it against the planner field by field; the GPU leg checks the part of it
+that shows: the sort columns, the planned spreader and its slabs from the mesh line, the pipeline from the stamp slots.
 
 Kernel keys: (family, Real where the family has one, R1, R2, energy-only flag where the family has one); 0, 0 are the staged / run-time forms.
 Thread-count variants are kept beside them as (family, Real or None, threads), and ("k_fftZInvMix", R1, R2, 512) per z pair."""
@@ -42,7 +43,7 @@ def _row(name, grid, nsub, fft, plane, path, env=None):
 #   and their y sizes 16*16, 15*16, 5*6, 5*8, 6*7, 12*15, 7*8, 10*12, 9*10, 8*9: every radix of the plane-radix list first and second on x and on
 #   y, except 5 second on y (UNREACHED_ROLES).  The Z rows add further splits.
 # Z rows: the z pairs the S and P rows cannot hold.  A z line of 108 .. 256 points fuses its forward pass into the merge kernel only over
-#   columns of 25 .. 42 cells (pme.hip launchSpreadOwn: 120 KB of LDS; double precision at nz = 256: 5 x 5 cells, 116 KB), so these planes are small.
+#   columns of 25 .. 42 cells (pme_plan.h ownSpread: 120 KB of LDS; double precision at nz = 256: 5 x 5 cells, 116 KB), so these planes are small.
 #   S, P and Z rows together hold every z pair with five subsets: k_spreadMerge fused in both precisions, k_fftZInvMix<A, B, 512>.
 # L rows: every pair size once on x, once on y, once on z on the three-pass pipeline: k_convolveX (x), k_fftStrided (y), k_fftZ (z) in double
 #   precision, and in single precision under SNB_NO_PLANE_FFT=1 (below 129 points nothing else takes the single-precision mesh off the plane
@@ -110,7 +111,7 @@ UNREACHED = {
 
 # Roles of the run-time plane kernel that no mesh can give it: {role: (file, function, condition, the row that shows the fallback)}
 UNREACHED_ROLES = {
-    "radix 5 as second factor on y": ("pme.hip", "planePathOK", "5 is second only in 25 = 5 * 5 (splitPlane orders r1 <= r2), and an odd ny is declined: (p.d.ny & 1)", "U25"),
+    "radix 5 as second factor on y": ("pme_plan.h", "planePath", "5 is second only in 25 = 5 * 5 (splitPlane orders r1 <= r2), and an odd ny is declined: (d.ny & 1)", "U25"),
 }
 
 
@@ -173,7 +174,7 @@ def plan(row, prec):
     px, py = pick(nx, L[0]), pick(ny, L[1])
     bricks = px > 0 and py > 0 and 8 * px * py * nz <= 60 * 1024
     out.update(cells=(px, py) if bricks else (0, 0), bricks=bricks)
-    # engine.hip planOwnSpread: margin 1 at this skin; slabs: the fewest whose region fits 40 KB (then 64 KB), more up to ~400 work-groups
+    # pme_plan.h ownSpreadMargin, ownSpread: margin 1 at this skin; slabs: the fewest whose region fits 40 KB (then 64 KB), more up to ~400 work-groups
     margin = max(1, int(np.ceil(0.5 * PADDING * max(nx / L[0], ny / L[1]) + 0.01)))
     assert margin == 1, row
     fixed = flt and "SNB_NO_FIXED_SPREAD" not in env
@@ -196,7 +197,7 @@ def plan(row, prec):
                     break
                 if nz % k == 0 and nz // k >= 8 and not (nz // k) & 1:
                     slabs = k
-    # pme.hip launchSpreadOwn: what can still decline it at the launch, the merge kernel's threads, the fused z pass
+    # ... what can still decline it at the launch, the merge kernel's threads, the fused z pass
     own = slabs >= 2
     if own:
         sz = nz // slabs
@@ -207,13 +208,13 @@ def plan(row, prec):
     nb = (px * py + 1) // 2
     fuse = own and "SNB_NO_FUSED_Z" not in env and 2 * real * (2 * nz * (nb + 1) + nz) <= 120 * 1024
     out.update(own=own, slabs=slabs if own else 0, fuse=fuse)
-    # pme.hip planePathOK
+    # pme_plan.h planePath (ok, buffers), zMix, convxThreads
     static = kind == "static"
     plane_lds = 8 * (nx * (ny | 1) + nx + (0 if static else ny))
     plane = (flt and fuse and "SNB_NO_PLANE_FFT" not in env and kind != "none" and ny % 2 == 0 and nsub <= 8 and plane_lds <= 156 * 1024
              and nx * (ny | 1) * 8 <= 156 * 1024)
     out["path"] = "plane" if plane else "three-pass"
-    out["zmix_nt"] = 512 if 8 * ((nsub + 1) // 2) >= 24 else 256
+    out["zmix_nt"] = 512 if 8 * ((nsub + 1) // 2) >= 24 and fft[2][0] else 256      # (the staged <0, 0> form exists at 256 threads only)
     out["convx_nt"] = 256 if (not flt and max(fft[0]) > 12) else 512
     out["plane_nt"] = int(env.get("SNB_PLANE_NT", 1024))
     return out

@@ -121,7 +121,7 @@ def ortho_ewald():
 
 def long_z():
     """6 x 6 x 64 = 2304 atoms in 3.0 x 3.25 x 31.2 nm, mesh 25 x 25 x 260: a z line of more than 256 points, which the planner of the own-atoms spreader
-    declines (engine.hip planOwnSpread): the scanning brick spreader runs.  Bricks
+    declines (csrc/pme_plan.h ownSpread): the scanning brick spreader runs.  Bricks
     of 260 points fit the spreader's LDS only as 5 x 5 columns, and 25 is the one legal size whose only divisor from 5 to 16 is 5: nx = ny here,
     over unequal lengths."""
     rng = np.random.default_rng(205)

@@ -1,15 +1,21 @@
 """The mesh-size census on the CPU: the table of tests/mesh_census.py is legal, the oracle evaluates every row, and the rows between them name
 every instantiation of the six (R1, R2) kernel families that the build holds -- read from the kernel names of the gfx950 code objects, so a
-pair added to pme.hip's FFT-pair or plane-pair list, or a new thread-count variant without a census row fails here, without a GPU.  The GPU leg
-(tests/test_gpu_mesh_census.py) asserts that the engine's own mesh line states each row's splits."""
+pair added to the FFT-pair or plane-pair list (csrc/pme_plan.h), or a new thread-count variant without a census row fails here, without a GPU.
+The engine's planner (csrc/pme_plan.h) runs here too, as a stand-alone program: its splits are the rows' words, its decisions those of
+mesh_census.plan().  The GPU leg (tests/test_gpu_mesh_census.py) asserts that the engine's own mesh line states each row's splits."""
 import copy
+import os
+import subprocess
 
 import numpy as np
 import pytest
 
 import mesh_census as M
 import recip_systems as R
+import shell_systems as S
 from test_host_cpu import _device_kernel_notes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("name", [r["name"] for r in M.ROWS])
@@ -90,3 +96,44 @@ def test_completeness_check_reports_a_removed_row(snb):
     assert missing <= own and not stale and not overlap
     _, variants = M.table_keys(rows)
     assert lib_variants - variants == {("k_fftZInvMix", 16, 16, 512)} and ("k_fftZInvMix", 16, 16, 512) in own_variants
+
+
+# ---- the planner on the CPU ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def planner(tmp_path_factory):
+    """tests/pme_plan_check.cpp (csrc/pme_plan.h, csrc/host_lists.h) under ASan + UBSan; the header alone first, with every warning an error and
+    no HIP include path."""
+    csrc = os.path.join(ROOT, "openmm-nonbonded-slicing_amd", "csrc")
+    flags = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", csrc]
+    tmp = tmp_path_factory.mktemp("pme_plan")
+    alone = tmp / "header_alone.cpp"
+    alone.write_text('#include "pme_plan.h"\n')
+    subprocess.check_call(flags + ["-fsyntax-only", str(alone)])
+    exe = tmp / "pme_plan_check"
+    subprocess.check_call(flags + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "pme_plan_check.cpp"), "-o", str(exe)])
+
+    def run(row, prec):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("SNB_")}
+        env.update(row["env"])
+        args = [str(v) for v in row["grid"] + (row["nsub"], 8 if prec == "double" else 4) + tuple(S.ORTHO_LENGTHS) + (M.N_ATOMS, M.PADDING)]
+        r = subprocess.run([str(exe)] + args, capture_output=True, text=True, env=env)
+        assert r.returncode == 0 and not r.stderr, "pme_plan_check %s exited with %d:\n%s" % (" ".join(args), r.returncode, r.stderr[-4000:])
+        return dict(line.split(" ", 1) for line in r.stdout.splitlines())
+    return run
+
+
+@pytest.mark.parametrize("name", [r["name"] for r in M.ROWS])
+def test_planner_states_the_rows_splits_and_agrees_with_plan(name, planner):
+    """The engine's planner, run on the CPU: the splits it prints are the row's own words (until now only the GPU leg saw the engine's), and
+    everything else it decides -- sort columns, bricks, slabs, whether the own-atoms spreader runs, the fused z pass, the pipeline, the thread
+    counts -- is what mesh_census.plan() restates."""
+    row = M.by_name(name)
+    for prec in ("single", "double"):
+        got, want = planner(row, prec), M.plan(row, prec)
+        assert got["fft"] == row["fft"] and got["plane"] == row["plane"], (name, prec, got)
+        assert tuple(int(v) for v in got["cells"].split()) == want["cells"], (name, prec, got, want)
+        assert bool(int(got["bricks"])) == want["bricks"] and got["group"] == ("1 1" if want["bricks"] else "0 0"), (name, prec, got, want)      # (columns of 5+ cells: one per brick)
+        assert bool(int(got["own"])) == want["own"] and (int(got["slabs"]) if want["own"] else 0) == want["slabs"] and got["margin"] == "1", (name, prec, got, want)
+        assert bool(int(got["fuse"])) == want["fuse"] and got["path"] == want["path"], (name, prec, got, want)
+        for k in ("zmix_nt", "convx_nt", "plane_nt") + (("merge_nt",) if "merge_nt" in want else ()):
+            assert int(got[k]) == want[k], (name, prec, k, got, want)
