@@ -43,7 +43,15 @@ template <bool FIXED, typename P> __device__ inline void fAddT(const P& p, float
     if constexpr (FIXED) __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(comp) + a * p.fs, toFixedForce(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else gAdd(comp + a * p.fs, v);
 }
-
+// The same accumulation at a 32-bit byte offset from the component's base (p.fBytes per atom slot; launches whose force arrays stay below
+// 2^31 bytes, pair_addressing.h): the atomic takes the base as its scalar operand and the offset as it stands, where the 64-bit index
+// above costs a multiply, a shift and an add per component.  loadAt: a load addressed the same way (list entries, tile headers, masks).
+template <typename T> __device__ __forceinline__ T loadAt(const void* base, unsigned byteOffset) { return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byteOffset); }
+template <bool FIXED> __device__ inline void fAddAt(float* comp, unsigned byteOffset, float v) {
+    char* const a = reinterpret_cast<char*>(comp) + byteOffset;
+    if constexpr (FIXED) __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(a), toFixedForce(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else gAdd(reinterpret_cast<float*>(a), v);
+}
 
 // Physical CU of the calling wave: XCC_ID[2:0] (hardware register 20) and the SE_ID | SH_ID | CU_ID bits 15:8 of HW_ID (register 4).
 // Used only to count co-resident work-groups of one launch (SNB_CU_SLOTS entries).
@@ -253,6 +261,14 @@ __device__ __forceinline__ void tileSteps(const DirectParams<Real>& p, const typ
 // cost the same either way).  8 steps; at step s lane c meets slots (c-2s) [component .x] and (c-2s-1) [component .y];
 // each component's j-force accumulator follows its slot with a two-lane DPP rotation per step.
 typedef float v2f __attribute__((ext_vector_type(2)));
+// a * b.yy in one v_pk_mul_f32 that reads the high half of b for both results (op_sel).  Written as a * b.yy the multiply is selected with
+// the broadcast operand's LOW half (op_sel_hi) wherever b is the second half of a 128-bit LDS read, behind a v_mov_b32 that copies the odd
+// register into the even one: six copies per four pair steps of tileStepsPacked.  Same operation, same rounding.
+// a * k.xx + k.yy with both constants in ONE scalar register pair.  A packed instruction takes a single scalar operand, so of two constants
+// held apart one is copied into a vector pair in every trip (v_mov_b64); the same pair named twice is one operand.  One fused multiply-add,
+// as the compiler contracts a * kx + ky.
+__device__ __forceinline__ v2f pkFmaK(v2f a, v2f k) { v2f r; asm("v_pk_fma_f32 %0, %1, %2, %2 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "s"(k)); return r; }
+__device__ __forceinline__ v2f pkMulHi(v2f a, v2f b) { v2f r; asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ inline float rowRor8(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true)); }
 
 // ---- the tile kernel ----------------------------------------------------------------------------
@@ -428,18 +444,20 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
                                                 v2f& fix, v2f& fiy, v2f& fiz, float& fjx, float& fjy, float& fjz, v2f& ecl, v2f& elj) {
 #pragma unroll UNROLL
     for (int s = 0; s < 8; s++) {
-        const float4 xj = rdPos[-s];
-        const float2 sj = rdSe[-s];
-        const v2f dx = pix - xj.x, dy = piy - xj.y, dz = piz - xj.z;
+        // (the j-slot as two-element vectors, for pkMulHi)
+        const v2f* const rp = reinterpret_cast<const v2f*>(rdPos - s);
+        const v2f xy = rp[0], zw = rp[1];
+        const v2f sj = *reinterpret_cast<const v2f*>(rdSe - s);
+        const v2f dx = pix - xy.xx, dy = piy - xy.yy, dz = piz - zw.xx;
         const v2f r2 = dx * dx + dy * dy + dz * dz;
         const v2f invR = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
         // Lennard-Jones (sigeps holds sigma/2 and 2 sqrt(eps))
-        v2f s2 = (sigi + sj.x) * invR; s2 = s2 * s2;
+        v2f s2 = (sigi + sj.xx) * invR; s2 = s2 * s2;
         const v2f s6 = s2 * s2 * s2;
-        const v2f es6 = (epsiS * sj.y) * s6;
-        v2f f = es6 * (s6 * 12.0f - 6.0f);
+        const v2f es6 = pkMulHi(epsiS, sj) * s6;
+        v2f f = es6 * pkFmaK(s6, v2f{12.0f, -6.0f});
         v2f eLJ = {0.f, 0.f}, eC = {0.f, 0.f};
-        if (ENERGY) eLJ = ((epsiRaw * sj.y) * s6) * (s6 - 1.0f);
+        if (ENERGY) eLJ = (pkMulHi(epsiRaw, sj) * s6) * (s6 - 1.0f);
         if (SWITCH) {
             // LJ switching function (ReferenceSlicedLJCoulombIxn.cpp:380-384, 428-431): branch-free, tt clamps to 0 below the switching distance
             const v2f r = r2 * invR;
@@ -466,19 +484,19 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
             const v2f fmul = (coef * 6.0f) * (1.0f - expd * dpre);
             f = f + fmul * lamL;
             if (ENERGY) {
-                const v2f sg = sigi + sj.x;
+                const v2f sg = sigi + sj.xx;
                 v2f sg2 = sg * sg; const v2f sg6 = (sg2 * sg2 * sg2) * p.invCut6;
-                eLJ = eLJ + coef * (1.0f - expd * epre) + (epsiRaw * sj.y) * ((1.0f - sg6) * sg6) - c6 * p.multShift6;
+                eLJ = eLJ + coef * (1.0f - expd * epre) + pkMulHi(epsiRaw, sj) * ((1.0f - sg6) * sg6) - c6 * p.multShift6;
             }
         }
         // Coulomb
-        const v2f qq = qiS * xj.w;
+        const v2f qq = pkMulHi(qiS, zw);
         v2f qqRaw = {0.f, 0.f};
-        if (ENERGY) qqRaw = qiRaw * xj.w;
+        if (ENERGY) qqRaw = pkMulHi(qiRaw, zw);
         if ((MC == MC_EWALD || MC == MC_LJPME) && POLY) {
             // [erfc(ar)/r + 2a/sqrt(pi) e^{-(ar)^2}] / r^2 = 1/r^3 - Bt(r^2), Bt a degree-11 polynomial in t = r^2 * ewScale - 1: no exp, no rcp (POLY: where the guard of ewald_fit.h keeps it)
             const v2f t = r2 * p.ewScale - 1.0f;
-            v2f bt = t * p.ewPoly[11] + p.ewPoly[10];
+            v2f bt = pkFmaK(t, v2f{p.ewPoly[11], p.ewPoly[10]});
 #pragma unroll
             for (int k = 9; k >= 0; k--) bt = bt * t + p.ewPoly[k];
             f = f * invR2 + qq * (invR2 * invR - bt);
@@ -543,7 +561,7 @@ __device__ __forceinline__ void tileStepsPacked(const DirectParams<float>& p, co
 //           reloads spilled SGPRs with v_readlane on every trip: 27 of the 59 VALU instructions a pair of unwanted tiles cost it over
 //           the forces kernel (docs/MEASUREMENT_LOG.md, "derivative tiles").
 enum { E_NONE = 0, E_RUNS = 1, E_TILES = 2 };
-template <int MC, bool POLY, int EMODE, bool SWITCH, bool FIXED>
+template <int MC, bool POLY, int EMODE, bool SWITCH, bool FIXED, bool WIDE>      // WIDE: 64-bit indices (fAddT), else 32-bit byte offsets (fAddAt, loadAt)
 __device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, const PairListParams<float>& q, const int nExclBlocks, const int nListBlocks) {
     constexpr bool ENERGY = EMODE != E_NONE, RUNS = EMODE == E_RUNS, TILES = EMODE == E_TILES;
     const int listBlock = p.listsLast ? (int)blockIdx.x - ((int)gridDim.x - nListBlocks) : (int)blockIdx.x;      // (CU-limited launch: list blocks last, see k_direct)
@@ -626,11 +644,18 @@ __device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, c
 #ifdef SNB_EXP_NO_JATOMICS      // experiment builds only (wrong forces): the kernel without its j-force scatter
     auto flushPending = [&]() { asm volatile("" :: "v"(pendX), "v"(pendY), "v"(pendZ), "v"(pendIdx)); };
 #else
-    auto flushPending = [&]() { if (pendIdx >= 0) { fAddT<FIXED>(p, p.fx, pendIdx, pendX); fAddT<FIXED>(p, p.fy, pendIdx, pendY); fAddT<FIXED>(p, p.fz, pendIdx, pendZ); } };
+    // (pendIdx: the atom slot, or without WIDE its byte offset in the force arrays, formed once per tile)
+    auto flushPending = [&]() {
+        if (pendIdx >= 0) {
+            if constexpr (WIDE) { fAddT<FIXED>(p, p.fx, pendIdx, pendX); fAddT<FIXED>(p, p.fy, pendIdx, pendY); fAddT<FIXED>(p, p.fz, pendIdx, pendZ); }
+            else { fAddAt<FIXED>(p.fx, pendIdx, pendX); fAddAt<FIXED>(p.fy, pendIdx, pendY); fAddAt<FIXED>(p.fz, pendIdx, pendZ); }
+        }
+    };
 #endif
     auto requestList = [&](TileRegs& r, int t) {                    // list entry + header of tile t
-        r.jcode = p.tileJ[t * 32 + stageJ];
-        const int2 v = *reinterpret_cast<const int2*>(&p.tileInfo[t + vzero]);
+        int2 v;
+        if constexpr (WIDE) { r.jcode = p.tileJ[t * 32 + stageJ]; v = *reinterpret_cast<const int2*>(&p.tileInfo[t + vzero]); }
+        else { r.jcode = loadAt<int>(p.tileJ, (unsigned)t * 128u + 4u * stageJ); v = loadAt<int2>(p.tileInfo, (unsigned)t * 16u + (unsigned)vzero); }
         r.slice = v.x; r.maskIdx = v.y;
     };
     auto requestAtoms = [&](TileRegs& r) {                          // needs r.jcode / r.slice / r.maskIdx (requested a tile earlier)
@@ -642,7 +667,8 @@ __device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, c
         const float4 sh = s_shift[(code >> SNB_JSHIFT_BITS) & 127];      // lattice image of the entry (table filled at kernel start)
         r.shx = sh.x; r.shy = sh.y; r.shz = sh.z;
         const int mi = r.maskIdx < 0 ? 0 : r.maskIdx;              // unconditional loads: a conditionally loaded register is a phi with a copy
-        r.mA = p.masks[mi * 32 + c]; r.mB = p.masks[mi * 32 + 16 + c];
+        if constexpr (WIDE) { r.mA = p.masks[mi * 32 + c]; r.mB = p.masks[mi * 32 + 16 + c]; }
+        else { const unsigned mo = 4u * (unsigned)(mi * 32 + c); r.mA = loadAt<unsigned>(p.masks, mo); r.mB = loadAt<unsigned>(p.masks, mo + 64u); }
         r.lam = *reinterpret_cast<const float2*>(&p.lambdas[2 * (r.slice & 0xFFFF)]);      // (the slice index comes with the tile header, written by the builder)
         if (ENERGY) r.need = p.sliceNeed[r.slice & 0xFFFF];      // energy steps: is this slice's energy wanted?
     };
@@ -687,12 +713,14 @@ __device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, c
         else if (RUNS && st.needE) { if (st.hasMask) SNB_TILE_PACKED(true, ENERGY, p.ewPolyE, ecl, elj); else SNB_TILE_PACKED(false, ENERGY, p.ewPolyE, ecl, elj); }
         else { if (st.hasMask) SNB_TILE_PACKED(true, false, p.ewPolyE, ecl, elj); else SNB_TILE_PACKED(false, false, p.ewPolyE, ecl, elj); }      // forces only (also: energy steps, slice not wanted)
 #undef SNB_TILE_PACKED
-        // rotate-then-subtract leaves lane c holding slot (c+1)&7: one more rotation brings every slot home, then the two
-        // partial sums of a slot (lanes c and c+8) are merged
-        fjx = rowRor1(fjx); fjy = rowRor1(fjy); fjz = rowRor1(fjz);
-        pendX = fjx + rowRor8(fjx); pendY = fjy + rowRor8(fjy); pendZ = fjz + rowRor8(fjz);
+        // rotate-then-subtract leaves lane c holding slot (c+1)&7, and lanes c and c+8 carry the two partial sums of a slot: these are
+        // merged where they lie (the add takes the rotated operand itself, v_add_f32_dpp), then one more rotation brings every slot
+        // home -- the same two terms in one add as rotating first, so the sum is the same in every bit
+        fjx = fjx + rowRor8(fjx); fjy = fjy + rowRor8(fjy); fjz = fjz + rowRor8(fjz);
+        pendX = rowRor1(fjx); pendY = rowRor1(fjy); pendZ = rowRor1(fjz);
         const int curCode = st.code;
-        pendIdx = (c < 8 && curCode != -1) ? (curCode & SNB_JIDX_MASK) : -1;      // entry c < 8 of quarter `row` == j-slot 8*row + c == the atom this lane staged
+        const int curJ = curCode & SNB_JIDX_MASK;
+        pendIdx = (c < 8 && curCode != -1) ? (WIDE ? curJ : (int)__umul24(curJ, p.fBytes)) : -1;      // entry c < 8 of quarter `row` == j-slot 8*row + c == the atom this lane staged
         st = stage(Y);
     };
     requestList(A, tBegin);
@@ -713,8 +741,14 @@ __device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, c
     ux += __shfl_xor(ux, 32, 64); uy += __shfl_xor(uy, 32, 64); uz += __shfl_xor(uz, 32, 64);
     int Iout = I;
     if constexpr (TILES) asm volatile("" : "+s"(Iout));      // (the i-atoms' 64-bit index is formed here, not held in two registers across the item's tiles)
+    if constexpr (WIDE) {
     if (row == 0) { fAddT<FIXED>(p, p.fx, (Iout * 32 + c), ox); fAddT<FIXED>(p, p.fy, (Iout * 32 + c), oy); fAddT<FIXED>(p, p.fz, (Iout * 32 + c), oz); }
     if (row == 1) { fAddT<FIXED>(p, p.fx, (Iout * 32 + 16 + c), ux); fAddT<FIXED>(p, p.fy, (Iout * 32 + 16 + c), uy); fAddT<FIXED>(p, p.fz, (Iout * 32 + 16 + c), uz); }
+    } else {
+    const unsigned oa = __umul24(Iout * 32 + c, p.fBytes), ob = __umul24(Iout * 32 + 16 + c, p.fBytes);
+    if (row == 0) { fAddAt<FIXED>(p.fx, oa, ox); fAddAt<FIXED>(p.fy, oa, oy); fAddAt<FIXED>(p.fz, oa, oz); }
+    if (row == 1) { fAddAt<FIXED>(p.fx, ob, ux); fAddAt<FIXED>(p.fy, ob, uy); fAddAt<FIXED>(p.fz, ob, uz); }
+    }
     if (RUNS) { if (curNeeded) flushEnergy(); curSlice = -1; curNeeded = false; }
     __builtin_amdgcn_wave_barrier();
     item = dyn ? wc.resolve(claimed) : item + nTileBlocks * 4;
@@ -723,13 +757,25 @@ __device__ __forceinline__ void directPackedBody(const DirectParams<float>& p, c
 }
 template <int MC, bool POLY, bool ENERGY, bool SWITCH, bool FIXED>
 __global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
-    directPackedBody<MC, POLY, ENERGY ? E_RUNS : E_NONE, SWITCH, FIXED>(p, q, nExclBlocks, nListBlocks);
+    directPackedBody<MC, POLY, ENERGY ? E_RUNS : E_NONE, SWITCH, FIXED, false>(p, q, nExclBlocks, nListBlocks);
 }
 // derivative steps (include_energy == 2): the same launch with the per-tile bookkeeping (no switching function: directKernel)
 template <int MC, bool POLY, bool FIXED>
 __global__ __launch_bounds__(256, 4) void k_directPackedSelected(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
-    directPackedBody<MC, POLY, E_TILES, false, FIXED>(p, q, nExclBlocks, nListBlocks);
+    directPackedBody<MC, POLY, E_TILES, false, FIXED, false>(p, q, nExclBlocks, nListBlocks);
 }
+// The same two kernels with 64-bit indices, for launches with a force or list array of 2^31 bytes or more (p.wideOffsets, set where the
+// engine fills DirectParams)
+namespace wide {
+template <int MC, bool POLY, bool ENERGY, bool SWITCH, bool FIXED>
+__global__ __launch_bounds__(256, 4) void k_directPacked(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
+    directPackedBody<MC, POLY, ENERGY ? E_RUNS : E_NONE, SWITCH, FIXED, true>(p, q, nExclBlocks, nListBlocks);
+}
+template <int MC, bool POLY, bool FIXED>
+__global__ __launch_bounds__(256, 4) void k_directPackedSelected(const DirectParams<float> p, const PairListParams<float> q, const int nExclBlocks, const int nListBlocks) {
+    directPackedBody<MC, POLY, E_TILES, false, FIXED, true>(p, q, nExclBlocks, nListBlocks);
+}
+}  // namespace wide
 
 // ---- energy-only tile kernels (steps with include_forces == 0) ------------------------------------
 // The raw slice energies of the same work items and tiles, from the same lane layout and the same per-lane accumulation order as the
@@ -907,10 +953,12 @@ template <typename Real, int MC> static TileKernel<Real> directKernel(const Dire
             // (one template switch for both polynomials: an energy step keeps them only where both passed the guard, engine.hip buildEwaldPoly)
             const int polyNeed = energy ? (SNB_POLY_FORCE | SNB_POLY_ENERGY) : SNB_POLY_FORCE;
             const bool poly = (MC == MC_EWALD || MC == MC_LJPME) && (p.ewUsePoly & polyNeed) == polyNeed;
-#define SNB_PACKED(P, E, S) return p.fixed ? k_directPacked<MC, P, E, S, true> : k_directPacked<MC, P, E, S, false>
+#define SNB_PACKED(P, E, S) do { if (p.wideOffsets) return p.fixed ? wide::k_directPacked<MC, P, E, S, true> : wide::k_directPacked<MC, P, E, S, false>; \
+                                 return p.fixed ? k_directPacked<MC, P, E, S, true> : k_directPacked<MC, P, E, S, false>; } while (0)
             // derivative steps: the per-tile form where it is free of scratch -- not with the switching function and not under LJPME, whose energy
             // bodies spill in either form (tests/test_host_cpu.py keeps the list of kernels that may); those keep the run-based kernel
-#define SNB_SELECTED(P) return p.fixed ? k_directPackedSelected<MC, P, true> : k_directPackedSelected<MC, P, false>
+#define SNB_SELECTED(P) do { if (p.wideOffsets) return p.fixed ? wide::k_directPackedSelected<MC, P, true> : wide::k_directPackedSelected<MC, P, false>; \
+                             return p.fixed ? k_directPackedSelected<MC, P, true> : k_directPackedSelected<MC, P, false>; } while (0)
             if constexpr (MC != MC_LJPME) {
                 if (energyMode == E_TILES && !p.useSwitch) {
                     if constexpr (MC == MC_NOCUTOFF) SNB_SELECTED(false);

@@ -11,6 +11,7 @@
 #include "host_lists.h"
 #include "ewald_fit.h"
 #include "pme_sizes.h"
+#include "pair_addressing.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1659,6 +1660,9 @@ public:
     void fillDirect(DirectParams<Real>& p, const int* need) {
         p.posq = posq.p; p.sigeps = sigeps.p; p.blockSubset = blockSubset.p; p.workItems = workItems.p;
         p.tileJ = tileJ.p; p.tileInfo = tileInfo.p; p.masks = masks.p; p.fx = fx.p; p.fy = fy.p; p.fz = fz.p; p.fs = fstride; p.fixed = fixedForces(); p.sliceE = sliceE.p; p.lambdas = dLambdas.p; p.sliceNeed = need;
+        // the packed kernels' addressing (pair_addressing.h): 32-bit byte offsets while every array they index that way allows it
+        const PairArrayExtents ext = {(int64_t)Npad, fstride, fixedForces(), (int64_t)std::min(tileJ.n / 32, tileInfo.n), (int64_t)(masks.n / 32)};
+        p.fBytes = (unsigned)forceSlotBytes(fstride, fixedForces()); p.wideOffsets = pairOffsetsFit32(ext) ? 0 : 1;
         const int r = cfg.shard_rank, c = cfg.shard_count;
         (void)r; (void)c;
         p.workStart = 0; p.workStride = 1; p.numWork = numWorkItems;      // the lists hold only the i-blocks this engine owns (block % shard_count == shard_rank)

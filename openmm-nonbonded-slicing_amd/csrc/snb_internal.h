@@ -69,6 +69,7 @@ template <typename Real> struct DirectParams {
     const int* tileJ;         // [T*32]
     const int4* tileInfo;     // [T]
     const unsigned* masks;    // [M*32]
+    unsigned fBytes; int wideOffsets;       // bytes of one atom slot in a component array (fs x 4, or x 8 when fixed); non-zero wideOffsets: the packed kernels index with 64 bits (pair_addressing.h)
     Real* fx; Real* fy; Real* fz; int fs;   // direct-space force accumulators: component bases and the index stride of an atom (1: three arrays; 4: one (x,y,z,-) record per atom)
     int fixed;                              // SNB_MIXED: the accumulators are 64-bit fixed point (2^32 per kJ/mol/nm) behind the same bases
     double* sliceE;           // [S*2] raw energies
