@@ -484,6 +484,52 @@ typedef struct {
 } snb_group_pair_batch;
 snb_status snb_evaluate_group_pair_energies(snb_handle h, const snb_group_pair_batch* b);
 
+/* -- per-slice virial tensors, at the current state and over stored frames --------------------- */
+/* The pressure tensor of a frame at every lambda state, split by slice and by Coulomb / van der Waals, from one evaluation:
+ *     slice_virials[f][s][t][c] = W_f[s][t][c] = - d E_raw[s][t] / d eps_c,     c over xx, yy, zz, xy, xz, yz,     kJ/mol
+ *     state_virials[f][k][c]    = sum_s sum_t state_lambdas[k][s][t] W_f[s][t][c]
+ * the derivative of the raw slice energy under the homogeneous deformation r -> (1 + eps) r of the box vectors and of every atom, at fixed
+ * pair set: the internal virial in  P_ab V = sum m v_a v_b + sum_s sum_t lambda[s][t] W[s][t][ab]  (the kinetic part is the caller's).
+ * E_raw is what an energy-only step with the same include flags leaves in snb_get_slice_energies: pairs inside the cutoff, Ewald
+ * exclusion corrections (the LJPME dispersion part into t = 1), 1-4 exceptions, the mesh sums, the neutralising background (with
+ * include_reciprocal) and the long-range dispersion correction (with include_direct, where coefficients are set); the Ewald self terms
+ * do not depend on the box.  W is raw -- not scaled by the lambdas and independent of them -- with the effective parameters, and
+ * symmetric: six components.  A pair adds d_a d_b f once, d as the kernels wrap it; the mesh part is the exact strain derivative of the
+ * mesh energy (at fixed fractional coordinates the mesh charges do not change), taken from the forward spectrum of every held mesh; the
+ * two closed forms go as 1 / V and add their energy to xx, yy and zz.  A non-periodic system has no box terms.  n_states == 0: the raw
+ * rows alone.  n_states > 0: state_virials, and the raw rows as well unless slice_virials is NULL; there is no cap on n_states.  Every
+ * entry of every requested output is written; rows of slices of an empty subset are zeros.  The sums are accumulated per wave and added
+ * to the working matrix with double atomics: equal from call to call up to the rounding of the sums, not bit for bit.
+ * With frames given the call follows the contract of snb_evaluate_frames: everything is checked before anything is enqueued; the list of
+ * frame f + 1 is built beside the pass of frame f, or in line, by the same rules; host frames go through the pinned staging; host output
+ * costs one synchronisation, at the end; device output is complete in stream order; afterwards positions, box, lambdas and mask are the
+ * caller's and the next snb_execute rebuilds; no step graph is captured or updated; frame steps count in snb_stats.n_rebuilds and in no
+ * timer; snb_get_frame_stats counts the batch and its frames.  With positions == NULL (n_frames must be 1) it is ONE evaluation of the
+ * engine's current box and positions and behaves as snb_evaluate_atom_forces behaves, a bound context included.
+ * In both forms it writes ONLY its outputs: the forces (snb_get_forces), the buffer of snb_set_force_output, a binding's buffers and the
+ * engine's slice-energy buffer (snb_get_slice_energies, snb_slice_energies_device) stay bit for bit what they were.
+ * NULL batch or handle, slice_virials NULL with n_states == 0, a negative n_states, n_states > 0 with NULL state_lambdas or
+ * state_virials, both include flags 0, a negative n_frames, positions == NULL with n_frames != 1: SNB_ERR_INVALID_ARGUMENT.
+ * shard_count > 1, SNB_Ewald with include_reciprocal (direct-only works): SNB_ERR_UNSUPPORTED.  n_frames == 0 (after these checks):
+ * SNB_OK, no work.  Frames given while a context is bound: SNB_ERR_STATE.  Box errors: as snb_evaluate_frames, with the frame index.
+ * The mesh part always takes the three-pass transforms (the plane path keeps its spectrum in LDS).  The working memory (the matrix
+ * double [64][S][2][6], the states) is allocated at the first call. */
+typedef struct {
+    int32_t        n_frames;
+    const void*    positions;        /* as snb_group_batch: [F][N][3] or [F][N][4]; NULL: the engine's CURRENT box and positions (n_frames must be 1) */
+    int32_t        is_device;
+    int32_t        is_double;
+    int32_t        stride4;
+    const double*  boxes;            /* HOST [F][9], reduced form, or NULL: the engine's current box for every frame */
+    int32_t        include_direct, include_reciprocal;
+    double*        slice_virials;    /* [F][S][2][6] raw (Coulomb, vdW) x (xx, yy, zz, xy, xz, yz), kJ/mol; may be NULL when n_states > 0 */
+    int32_t        out_is_device;
+    int32_t        n_states;         /* K >= 0 lambda states */
+    const double*  state_lambdas;    /* HOST [K][S][2] */
+    double*        state_virials;    /* [F][K][6]; same residence as slice_virials */
+} snb_virial_batch;
+snb_status snb_evaluate_slice_virials(snb_handle h, const snb_virial_batch* b);
+
 /* -- queries ----------------------------------------------------------------------------------- */
 snb_status snb_get_pme_parameters(snb_handle h, double* alpha, int32_t grid[3]);
 snb_status snb_get_ljpme_parameters(snb_handle h, double* alpha, int32_t grid[3]);

@@ -20,7 +20,7 @@ SYMBOLS = [
     "snb_rebuild_neighbors", "snb_execute", "snb_get_forces", "snb_set_force_output", "snb_set_shard_blocks", "snb_get_slice_energies", "snb_slice_energies_device", "snb_synchronize",
     "snb_get_pme_parameters", "snb_get_ljpme_parameters", "snb_get_stats", "snb_reset_timers", "snb_set_timing_interval", "snb_legal_grid_size", "snb_abi_version",
     "snb_test_fft3d", "snb_bind_context", "snb_context_order_changed", "snb_evaluate_frames", "snb_get_frame_stats", "snb_evaluate_atom_energies",
-    "snb_evaluate_atom_forces", "snb_evaluate_group_energies", "snb_evaluate_group_forces", "snb_evaluate_group_pair_energies",
+    "snb_evaluate_atom_forces", "snb_evaluate_group_energies", "snb_evaluate_group_forces", "snb_evaluate_group_pair_energies", "snb_evaluate_slice_virials",
 ]
 
 SNB_OK, SNB_ERR_INVALID_ARGUMENT, SNB_ERR_HIP, SNB_ERR_BOX_TOO_SMALL, SNB_ERR_NOT_PME, SNB_ERR_STATE, SNB_ERR_UNSUPPORTED = range(7)
@@ -100,6 +100,17 @@ class SnbGroupPairBatch(ctypes.Structure):
     ]
 
 
+class SnbVirialBatch(ctypes.Structure):
+    """snb_virial_batch: F stored frames (or the current state), raw rows and K lambda states, for snb_evaluate_slice_virials
+    (include/snb.h)."""
+    _fields_ = [
+        ("n_frames", ctypes.c_int32), ("positions", ctypes.c_void_p), ("is_device", ctypes.c_int32), ("is_double", ctypes.c_int32),
+        ("stride4", ctypes.c_int32), ("boxes", ctypes.POINTER(ctypes.c_double)), ("include_direct", ctypes.c_int32), ("include_reciprocal", ctypes.c_int32),
+        ("slice_virials", ctypes.c_void_p), ("out_is_device", ctypes.c_int32), ("n_states", ctypes.c_int32),
+        ("state_lambdas", ctypes.POINTER(ctypes.c_double)), ("state_virials", ctypes.c_void_p),
+    ]
+
+
 class SnbFrameStats(ctypes.Structure):
     _fields_ = [
         ("n_batches", ctypes.c_int64), ("n_frames", ctypes.c_int64), ("n_built_beside", ctypes.c_int64), ("n_built_in_line", ctypes.c_int64),
@@ -170,6 +181,7 @@ def lib():
     L.snb_evaluate_group_energies.argtypes = [vp, ctypes.POINTER(SnbGroupBatch)]
     L.snb_evaluate_group_forces.argtypes = [vp, ctypes.POINTER(SnbGroupForceBatch)]
     L.snb_evaluate_group_pair_energies.argtypes = [vp, ctypes.POINTER(SnbGroupPairBatch)]
+    L.snb_evaluate_slice_virials.argtypes = [vp, ctypes.POINTER(SnbVirialBatch)]
     for name in SYMBOLS:
         getattr(L, name)  # AttributeError if the header and the library ever diverge
     _lib = L

@@ -68,6 +68,37 @@ def calcEwaldParameters(force, boxVectors):
     return alpha, find(boxVectors[0][0]), find(boxVectors[1][1]), find(boxVectors[2][2])
 
 
+VIRIAL_COMPONENTS = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))      # the six entries of a virial row: xx, yy, zz, xy, xz, yz
+KJ_PER_MOL_NM3_IN_BAR = 16.6053906717      # 1 kJ/mol/nm^3 = 1e3 J / N_A / 1e-27 m^3 = 1.66053906717e6 Pa
+
+
+def virialMatrix(rows):
+    """Virial rows [..., 6] (xx, yy, zz, xy, xz, yz) as symmetric matrices [..., 3, 3]."""
+    rows = np.asarray(rows, dtype=np.float64)
+    out = np.zeros(rows.shape[:-1] + (3, 3))
+    for c, (a, b) in enumerate(VIRIAL_COMPONENTS):
+        out[..., a, b] = rows[..., c]
+        out[..., b, a] = rows[..., c]
+    return out
+
+
+def virialsAtStates(rows, lambdaStates):
+    """The virial [..., K, 6] that per-slice rows [..., S, 2, 6] imply at the lambda states [K][S][2]:
+    ``sum_s sum_t lambdaStates[k][s][t] rows[..., s, t, :]`` -- the NumPy statement of state_virials."""
+    rows = np.asarray(rows, dtype=np.float64); lam = np.asarray(lambdaStates, dtype=np.float64)
+    return np.einsum("kst,...stc->...kc", lam.reshape(-1, rows.shape[-3], 2), rows)
+
+
+def pressureFromVirial(virial, volume, kinetic=None):
+    """The pressure tensor ``P = (kinetic + virial) / volume`` in kJ/mol/nm^3, from the internal virial (rows [..., 6] or matrices
+    [..., 3, 3], kJ/mol, e.g. a row of virialsAtStates), the volume in nm^3 and, when given, the kinetic part ``sum_i m_i v_ia v_ib`` in
+    the same shape and unit (None: the virial pressure alone).  Multiply by KJ_PER_MOL_NM3_IN_BAR = 16.6053906717 for bar."""
+    p = np.asarray(virial, dtype=np.float64)
+    if kinetic is not None:
+        p = p + np.asarray(kinetic, dtype=np.float64)
+    return p / float(volume)
+
+
 class HipCalcSlicedNonbondedForceKernel:
     """MI355X kernel object behind the reference's ``CalcSlicedNonbondedForceKernel`` interface."""
 
@@ -682,6 +713,80 @@ class HipCalcSlicedNonbondedForceKernel:
             out[k] = K.groupAtomEnergies(K.forcesFromAtomForces(table, subsets, lam[k]), groups)
         return out
 
+    # -- per-slice virial tensors (include/snb.h, snb_evaluate_slice_virials) ------------------------
+    def _virialOutputs(self, b, F, lambdaStates, keep):
+        """Host outputs of a virial batch: rows (F, S, 2, 6) and, with lambdaStates [K][S][2], stateVirials (F, K, 6)."""
+        rows = np.zeros((F, self.numSlices, 2, 6))
+        b.slice_virials = rows.ctypes.data_as(ctypes.c_void_p); b.out_is_device = 0
+        states = None
+        if lambdaStates is not None:
+            lam = np.ascontiguousarray(np.asarray(lambdaStates, dtype=np.float64).reshape(-1, self.numSlices, 2))
+            keep.append(lam)
+            states = np.zeros((F, lam.shape[0], 6))
+            b.n_states = lam.shape[0]; b.state_lambdas = _dp(lam); b.state_virials = states.ctypes.data_as(ctypes.c_void_p)
+        return rows, states
+
+    def computeSliceVirials(self, context, includeDirect=True, includeReciprocal=True, lambdaStates=None, devicePointer=None):
+        """Per-slice virial tensors at the context's positions, box and parameters (include/snb.h, snb_evaluate_slice_virials with
+        positions == NULL): ``W[s][t][c] = -dE_raw[s][t]/d eps_c`` under a homogeneous deformation of the box and of every atom, (S, 2, 6)
+        with t = (Coulomb, vdW) and c over xx, yy, zz, xy, xz, yz, in kJ/mol -- the internal virial of the pressure tensor, by slice and
+        term, from one evaluation.  Not scaled by the lambdas.  lambdaStates [K][S][2]: then the result is (rows, stateVirials (K, 6)),
+        the virial at every lambda state (virialsAtStates of the rows).  devicePointer: address of a double [S][2][6] array on the
+        engine's device that takes the rows -- with lambdaStates a pair (rows address or None, address of a double [K][6] array) --
+        complete in stream order; then None is returned.  Forces, force outputs and the slice energies of the last steps stay as they
+        are.  See virialMatrix and pressureFromVirial."""
+        self._push_state(context)
+        b = _capi.SnbVirialBatch()
+        b.n_frames = 1; b.include_direct = int(bool(includeDirect)); b.include_reciprocal = int(bool(includeReciprocal))
+        keep = []
+        if devicePointer is None:
+            rows, states = self._virialOutputs(b, 1, lambdaStates, keep)
+            self._check(self._lib.snb_evaluate_slice_virials(self._h, ctypes.byref(b)))
+            return rows[0] if states is None else (rows[0], states[0])
+        b.out_is_device = 1
+        if lambdaStates is None:
+            b.slice_virials = ctypes.c_void_p(int(devicePointer))
+        else:
+            rowsPtr, statesPtr = devicePointer
+            lam = np.ascontiguousarray(np.asarray(lambdaStates, dtype=np.float64).reshape(-1, self.numSlices, 2))
+            b.slice_virials = ctypes.c_void_p(int(rowsPtr)) if rowsPtr is not None else None
+            b.n_states = lam.shape[0]; b.state_lambdas = _dp(lam); b.state_virials = ctypes.c_void_p(int(statesPtr))
+        self._check(self._lib.snb_evaluate_slice_virials(self._h, ctypes.byref(b)))
+        return None
+
+    def computeSliceVirialsForFrames(self, context, positions=None, boxes=None, includeDirect=True, includeReciprocal=True, lambdaStates=None,
+                                     positionsDevicePointer=None, numFrames=None):
+        """Per-slice virial tensors [F][S][2][6] of F stored frames in one call (include/snb.h, snb_evaluate_slice_virials): the pressure
+        tensor of a trajectory by slice and term -- surface tensions, osmotic pressures, stress autocorrelations, the pressure at every
+        alchemical state -- through the frame pipeline of computeSliceEnergiesForFrames.  positions, boxes, positionsDevicePointer,
+        numFrames: as in computeSliceEnergiesForFrames.  lambdaStates [K][S][2]: then the result is (rows, stateVirials (F, K, 6)),
+        contracted on the device.  Parameters are pushed from the context first; the context's own positions, the forces and the slice
+        energies of the last steps stay as they are."""
+        self._push_frame_state(context)
+        b = _capi.SnbVirialBatch()
+        b.include_direct = int(bool(includeDirect)); b.include_reciprocal = int(bool(includeReciprocal))
+        if positions is None and positionsDevicePointer is None:
+            raise OpenMMException("computeSliceVirialsForFrames: positions or positionsDevicePointer must be given (computeSliceVirials evaluates the context's own state)")
+        F, keep = self._frames_into(b, "computeSliceVirialsForFrames", positions, boxes, positionsDevicePointer, numFrames)
+        rows, states = self._virialOutputs(b, F, lambdaStates, keep)
+        self._check(self._lib.snb_evaluate_slice_virials(self._h, ctypes.byref(b)))
+        return rows if states is None else (rows, states)
+
+    @staticmethod
+    def virialMatrix(rows):
+        """Virial rows [..., 6] (xx, yy, zz, xy, xz, yz) as symmetric matrices [..., 3, 3]."""
+        return virialMatrix(rows)
+
+    @staticmethod
+    def virialsAtStates(rows, lambdaStates):
+        """The virial [..., K, 6] the rows [..., S, 2, 6] imply at the lambda states [K][S][2] -- the NumPy statement of state_virials."""
+        return virialsAtStates(rows, lambdaStates)
+
+    @staticmethod
+    def pressureFromVirial(virial, volume, kinetic=None):
+        """See the module-level pressureFromVirial."""
+        return pressureFromVirial(virial, volume, kinetic)
+
     def getFrameStats(self):
         st = _capi.SnbFrameStats()
         self._check(self._lib.snb_get_frame_stats(self._h, ctypes.byref(st)))
@@ -797,6 +902,9 @@ class SlicedNonbondedForceImpl:
 
     def getGroupPairEnergies(self, context, labels, **options):
         return self.kernel.computeGroupPairEnergies(context, labels, **options)
+
+    def getSliceVirials(self, context, **options):
+        return self.kernel.computeSliceVirials(context, **options)
 
 
 class System:
@@ -922,6 +1030,16 @@ class Context:
         for impl in self._impls:
             if impl.owner is force:
                 return impl.getGroupPairEnergies(self, labels, **options)
+        raise OpenMMException("force not in this context")
+
+    def getSliceVirials(self, force, **options):
+        """Per-slice virial tensors of ``force``, (S, 2, 6) over xx, yy, zz, xy, xz, yz, with lambdaStates also (K, 6):
+        HipCalcSlicedNonbondedForceKernel.computeSliceVirials."""
+        if self._positions is None:
+            raise OpenMMException("Particle positions have not been set")
+        for impl in self._impls:
+            if impl.owner is force:
+                return impl.getSliceVirials(self, **options)
         raise OpenMMException("force not in this context")
 
     def getAtomForces(self, force, **options):

@@ -127,6 +127,7 @@ struct EngineBase {
     virtual void evaluateGroupEnergies(const snb_group_batch*) = 0;
     virtual void evaluateGroupForces(const snb_group_force_batch*) = 0;
     virtual void evaluateGroupPairEnergies(const snb_group_pair_batch*) = 0;
+    virtual void evaluateSliceVirials(const snb_virial_batch*) = 0;
     virtual void getFrameStats(snb_frame_stats*) = 0;
 };
 
@@ -2136,6 +2137,96 @@ public:
         runFrames(in, t0, [&](int f) { pass(f, std::max(Npad, npadPredict)); }, deliver);
     }
 
+    // ------------------------------------------------------------------------------------------
+    // Per-slice virial tensors, at the current state and over stored frames (snb_evaluate_slice_virials):
+    // W[s][t][c] = -dE_raw[s][t]/d eps_c under a homogeneous deformation of box and atoms.  The frame, the refusals and the neighbour-list
+    // rules of evaluateGroups above, with a step of its own: gather, zero fill, the tile launch of virial.hip with the direct parameters of
+    // the atom pass, per mesh the three-pass front with the plane path off (the spectrum must reach memory) and the Gram kernel, the finish
+    // into the frame's row.  Writes only its outputs: the working matrix, the device copy of the states, a row of its own when only the
+    // states are asked for and the staging of a host result are its own.
+    // ------------------------------------------------------------------------------------------
+    DevBuf<double> virialTab, virialRow, virialOut, virialStates, dVirialLambdas;
+    void evaluateSliceVirials(const snb_virial_batch* b) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::string who = "snb_evaluate_slice_virials";
+        const int F = b->n_frames, K = b->n_states;
+        const FrameInput in{"snb_evaluate_slice_virials", F, b->positions, b->is_device == 0, b->is_double != 0, b->stride4 != 0, b->boxes};
+        // ---- everything is checked before anything is enqueued or changed
+        if (K < 0) { err = who + ": negative state count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (K > 0 ? !(b->state_lambdas && b->state_virials) : !b->slice_virials) { err = who + ": " + (K > 0 ? "state_lambdas and state_virials" : "slice_virials") + " must be given"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        const bool direct = b->include_direct != 0, recip = b->include_reciprocal != 0;
+        refuseAtomCall(who, nullptr, nullptr, direct, recip, true, false);
+        if (F < 0) { err = who + ": negative frame count"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        refuseAtomCall(who, nullptr, nullptr, direct, recip, false, true);
+        if (F == 0) return;
+        if (!in.positions && F != 1) { err = who + ": positions == NULL evaluates the engine's current state: n_frames must be 1"; throw (int)SNB_ERR_INVALID_ARGUMENT; }
+        if (in.positions && ctx.on) { err = who + ": frames were given while a context is bound (snb_bind_context): the positions come from its posq"; throw (int)SNB_ERR_STATE; }
+        if (in.positions) checkFrames(in, recip);
+        const size_t rowLen = (size_t)S * 12, stateLen = (size_t)K * 6;
+        const bool wantRows = b->slice_virials != nullptr, hostOut = b->out_is_device == 0;
+        double* rows = b->slice_virials; double* states = b->state_virials;
+        auto prepare = [&]() {      // the states: one upload per call, through the pinned ring
+            if (K > 0) pinned.upload(dVirialLambdas, std::vector<double>(b->state_lambdas, b->state_lambdas + (size_t)K * S * 2), stream);
+            virialTab.resize((size_t)SNB_SLICE_E_PARTS * rowLen);
+            if (!wantRows) virialRow.resize(rowLen);
+            else if (hostOut) { virialOut.resize((size_t)F * rowLen); rows = virialOut.p; }
+            if (hostOut && K > 0) { virialStates.resize((size_t)F * stateLen); states = virialStates.p; }
+        };
+        auto pass = [&](int f) {
+            const bool mesh = recip && isPme() && nGrids > 0;
+            const bool cellsReady = enqueueGather(mesh, false, false, 0);      // sorted positions, the Coulomb-mesh cells, the displacement watch; nothing cleared
+            launchZeroFill(virialTab.p, sizeof(double) * SNB_SLICE_E_PARTS * rowLen, stream);
+            const int* const need = sliceNeed(StepEnergy::All);
+            if (direct) {
+                DirectParams<Real> p; PairListParams<Real> q;
+                std::memset(&p, 0, sizeof(p)); std::memset(&q, 0, sizeof(q));
+                fillDirect(p, need); fillPairLists(q, need);
+                launchVirialTiles<Real>(p, methodClass(), wrapMode, &q, virialTab.p, stream);
+            }
+            if (mesh) {
+                double r[9]; recipBoxRows(box, r);
+                auto one = [&](PmePlan<Real>& m) {      // the unmixed forward spectrum of one mesh, then its Gram sums
+                    PmeParams<Real> pp;
+                    std::memset(&pp, 0, sizeof(pp));
+                    fillPme(pp, m, false, need, cellsReady); pp.mix = 0; pp.planeB = nullptr; pp.planeEterm = nullptr;
+                    const int zDone = launchPmeSpread<Real>(pp, stream);
+                    if (zDone == 2) throw HipError{who + ": the spreader took the plane path with its buffers withheld"};
+                    launchPmeForwardFFT<Real>(pp, stream, zDone == 1);
+                    launchPmeFFTX<Real>(pp, -1, stream);
+                    VirialMesh<Real> v;
+                    std::memset(&v, 0, sizeof(v));
+                    v.spectrum = pp.gridCplx; v.modx = pp.modx; v.mody = pp.mody; v.modz = pp.modz; v.gridSubset = pp.gridSubset;
+                    v.nx = pp.d.nx; v.ny = pp.d.ny; v.nz = pp.d.nz; v.nzc = pp.d.nzc; v.nsub = pp.nsub; v.nsubTotal = nsub; v.dispersion = pp.dispersion;
+                    for (int i = 0; i < 9; i++) v.recip[i] = r[i];
+                    v.alpha = m.alpha; v.volume = box[0] * box[4] * box[8];
+                    launchVirialGram<Real>(v, virialTab.p, stream);
+                };
+                one(pme);
+                if (cfg.method == SNB_LJPME) one(dpme);
+            }
+            SliceFinish fin; std::memset(&fin, 0, sizeof(fin));
+            if (isPeriodic()) fin = makeSliceFinish(direct, recip);
+            launchVirialFinish(virialTab.p, S, fin, wantRows ? rows + (size_t)f * rowLen : virialRow.p, dVirialLambdas.p, K, K > 0 ? states + (size_t)f * stateLen : nullptr, stream);
+        };
+        auto deliver = [&]() {
+            if (!hostOut) return false;
+            if (wantRows) HIPCHECK(hipMemcpyAsync(b->slice_virials, rows, sizeof(double) * (size_t)F * rowLen, hipMemcpyDeviceToHost, stream));
+            if (K > 0) HIPCHECK(hipMemcpyAsync(b->state_virials, states, sizeof(double) * (size_t)F * stateLen, hipMemcpyDeviceToHost, stream));
+            HIPCHECK(hipStreamSynchronize(stream));
+            return true;
+        };
+        if (!in.positions) {      // the engine's current state, as the atom calls take it
+            beginExecute(false, recip);
+            prepare();
+            pass(0);
+            endExecute();
+            deliver();
+            return;
+        }
+        prepare();
+        runFrames(in, t0, pass, deliver);
+    }
+
     // classic Ewald: half-space k-vectors in the reference's enumeration order (ReferenceSlicedLJCoulombIxn.cpp:288-355)
     void runEwald(bool energy, bool forces) {
         if (hKvec.empty()) {
@@ -2416,6 +2507,10 @@ snb_status snb_evaluate_group_forces(snb_handle h, const snb_group_force_batch* 
 snb_status snb_evaluate_group_pair_energies(snb_handle h, const snb_group_pair_batch* b) {
     if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_group_pair_energies: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
     return guard(h, [&] { h->impl->evaluateGroupPairEnergies(b); });
+}
+snb_status snb_evaluate_slice_virials(snb_handle h, const snb_virial_batch* b) {
+    if (!b) { if (h && h->impl) h->impl->err = "snb_evaluate_slice_virials: null batch"; return SNB_ERR_INVALID_ARGUMENT; }
+    return guard(h, [&] { h->impl->evaluateSliceVirials(b); });
 }
 snb_status snb_get_frame_stats(snb_handle h, snb_frame_stats* out) { if (!out) return SNB_ERR_INVALID_ARGUMENT; return guard(h, [&] { h->impl->getFrameStats(out); }); }
 

@@ -352,6 +352,21 @@ void launchGroupPairLabels(const int* labelsUser, const int* sortedToUser, int n
 template <typename Real> void launchGroupPairTiles(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, const int* labelSorted, double* M, int parts,
                                                    size_t stride, hipStream_t s);
 void launchGroupPairFinish(const double* M, size_t n, int parts, double* row, hipStream_t s);
+// per-slice virial tensors (virial.hip, snb_evaluate_slice_virials): W = double [SNB_SLICE_E_PARTS][S][2][6] (xx, yy, zz, xy, xz, yz), added
+// to -- a work-group into copy blockIdx mod SNB_SLICE_E_PARTS.  Tiles and the two pair lists: d_a d_b f of every pair, once.
+template <typename Real> void launchVirialTiles(const DirectParams<Real>& p, int methodClass, bool wrap, const PairListParams<Real>* lists, double* W, hipStream_t s);
+// ... and the mesh part, from the forward spectrum of the held meshes as the three-pass front leaves it (launchPmeSpread that did not
+// return 2, launchPmeForwardFFT, launchPmeFFTX(-1)); box, alpha and volume in double
+template <typename Real> struct VirialMesh {
+    const typename Vec<Real>::T2* spectrum;      // [nsub][nx][ny][nzc]
+    const Real* modx; const Real* mody; const Real* modz;
+    const int* gridSubset;                       // [nsub] subset id of each held mesh
+    int nx, ny, nz, nzc, nsub, nsubTotal, dispersion;
+    double recip[9], alpha, volume;
+};
+template <typename Real> void launchVirialGram(const VirialMesh<Real>& p, double* W, hipStream_t s);
+// row[S][2][6] = the copies in index order + the closed forms that go as 1 / V; nStates > 0: states[k][6] = the row contracted with stateLambdas[k][S][2] (device)
+void launchVirialFinish(const double* W, int nSlices, const SliceFinish& f, double* row, const double* stateLambdas, int nStates, double* states, hipStream_t s);
 template <typename Real> int launchPmeSpread(const PmeParams<Real>& p, hipStream_t s);   // 1: forward z FFT already done; 2: ... and the spectrum is plane-major (plane path)
 template <typename Real> bool launchPlaneEterm(const PmeParams<Real>& p, Real* table, hipStream_t s);   // rebuild time: fills the plane path's kernel-value table
 template <typename Real> void launchPmePlanePath(const PmeParams<Real>& p, hipStream_t s);   // after a spreader that returned 2: k_planeXY + k_fftZInvMix instead of forward FFT, convolution, inverse FFT
